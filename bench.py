@@ -14,9 +14,21 @@ it, VALU issue: its VALU wave-instructions per launch (rocprofv3 SQ_INSTS_VALU p
 under profiles/, times the launch's rays) over its HIP-event-measured duration, against the issue
 peak of 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 instruction; beside it the measured HBM bytes
 (hbm_frac) and the reference-equivalent bytes of SURVEY.md 8(d) (ref_equiv: served by caches, not
-a ceiling).  `parity` compares the last timed step's image with the reference as shipped on the
-same per-path streams (tests/golden fixture), after the timed region.  `cpu_baseline` times the
-reference itself (oracle/_ref/mrt_ref, as shipped) on a bounded sample on this host.
+a ceiling).
+
+A plain run does only what `value` needs: set up, warm up, time the K steps, write the outputs
+(--dump-outputs) and print the line.  With --full it also measures and checks the rest, after the
+timed region: `parity` compares the last timed step's image with the reference as shipped on the
+same per-path streams (tests/golden fixture), `other_numerics` times the other numerics contract,
+`other_walk` the general hit walk, and `cpu_baseline` times the reference itself
+(oracle/_ref/mrt_ref, as shipped) on a bounded sample on this host; each of them can be left out
+of a --full run with its --no-... option.  Without --full those objects are null.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): DIR/image.npy, the assembled
+float32 RGBA framebuffer [height, width, 4] (what render_device / the gather hand the caller), and
+DIR/rays.npy, the rays of one step (float64 [1]).  A framebuffer above 48 MB is written as a fixed
+seeded sample of its pixels, with their indices in DIR/image_index.npy (float64).  The scene
+builders are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -60,13 +72,20 @@ def parse():
     ap.add_argument("--depth", type=int, default=32)
     ap.add_argument("--tile-size", type=int, default=8,
                     help="work_queue tile edge; also the multi-GPU partition grain (tiles dealt to the ranks in permuted rounds of N)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: parity "
+                         "against the reference fixture, the other numerics contract, the general hit walk, the CPU "
+                         "baseline (each has a --no-... option); off by default, a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (image: float32 [H, W, 4] "
+                         "framebuffer, rays: float64 rays per step; a framebuffer above 48 MB as a seeded pixel sample)")
     ap.add_argument("--cpu-spp", type=int, default=256, help="spp of the bounded CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-quick", action="store_true", help="time the CPU baseline on the quota threads only")
     ap.add_argument("--numerics", choices=["fast", "exact"], default="fast",
                     help="numerics contract of the timed render: fast = tolerance contract (per-pixel RMSE < 1e-3 "
                          "vs the reference as shipped, tests/test_gpu_parity.py), exact = bit-for-bit the reference "
-                         "built exact; the other one is timed too and reported as other_numerics")
+                         "built exact; with --full the other one is timed too and reported as other_numerics")
     ap.add_argument("--no-compare-numerics", action="store_true")
     ap.add_argument("--kernel-reps", type=int, default=0,
                     help="ignored (kept for old command lines): the roofline's kernel time is now the HIP-event "
@@ -116,7 +135,29 @@ def parse():
                     help="record a HIP event after every timed step (on its stream) and report the per-step "
                          "completion intervals (median / p90 / max and where the max fell): tells a whole-run "
                          "slowdown (clock) from single-step stalls (rehearsal diagnosis)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps alone
+        args.no_cpu_baseline = args.no_compare_numerics = args.no_other_walk = args.no_parity = True
+    return args
+
+
+DUMP_MAX_BYTES = 48 << 20  # image + index; --dump-outputs stays well under 64 MB in all
+
+
+def dump_outputs(path, image, rays_per_step, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the last timed step's framebuffer and ray count as .npy (float32 / float64).
+    A framebuffer above max_bytes: the same seeded sample of its pixels in every run, in pixel
+    order, with the pixel indices beside it (sample and indices together within max_bytes)."""
+    os.makedirs(path, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes > max_bytes:
+        flat = img.reshape(-1, img.shape[-1])
+        n = max_bytes // (flat.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], size=n, replace=False))
+        np.save(os.path.join(path, "image_index.npy"), idx.astype(np.float64))
+        img = flat[idx]
+    np.save(os.path.join(path, "image.npy"), img)
+    np.save(os.path.join(path, "rays.npy"), np.array([rays_per_step], dtype=np.float64))
 
 
 def _cpu_quota():
@@ -582,6 +623,9 @@ def main():
         full = np.zeros((args.width * args.height, 4), dtype=np.float32)
         full[px] = outs[(it[0] - 1) % nbuf][:n_local].cpu().numpy()
         return full.reshape(args.height, args.width, 4)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_image(), nrays // args.steps)
 
     # parity of the timed render (after the timed region): the last step's image against the
     # reference as shipped on the same per-path streams, when a fixture of this exact config exists

@@ -278,10 +278,9 @@ def test_select_scene_errors_are_loud(mrt, tmp_path):
 
 
 def test_packed_mesh_equals_obj_parse(mrt, tmp_path):
-    """assets/*.mesh hold exactly the records the OBJ parser produces (checked where the OBJ exists)."""
-    obj = "/root/reference/obj/bunny.obj"
-    if not os.path.exists(obj):
-        pytest.skip("reference OBJ not present on this host")
+    """assets/*.mesh hold exactly the records the OBJ parser produces (tests/golden/bunny.obj: the
+    reference's bunny mesh as it reads it)."""
+    obj = os.path.join(ROOT, "tests", "golden", "bunny.obj")
     out = tmp_path / "bunny.mesh"
     assert mrt.lib().mrt_pack_obj(obj.encode(), str(out).encode()) == 0
     assert out.read_bytes() == open(os.path.join(ROOT, "assets", "bunny.mesh"), "rb").read()
@@ -314,6 +313,35 @@ def test_bench_roofline_prices_pmc_per_ray(tmp_path):
     assert half["frac"] == pytest.approx(r["frac"], rel=1e-3) and half["hbm_frac"] == pytest.approx(r["hbm_frac"], rel=1e-3)
     args.width = 640
     assert bench.roofline(args, 8.0, 778e6, "fast", ki)["frac"] is None
+
+
+def test_bench_dump_outputs_and_plain_run_options(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the framebuffer as float32 and the rays as float64 .npy; a framebuffer
+    above the size cap as the same seeded pixel sample in every run, sample and indices within the
+    cap.  A plain run switches everything but the timed steps off; --full leaves it on."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    img = np.random.default_rng(1).random((37, 23, 4)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), img, 12345)
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img) and not (tmp_path / "a" / "image_index.npy").exists()
+    rays = np.load(tmp_path / "a" / "rays.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [12345.0]
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), img, 12345, max_bytes=4800)
+    sub, idx = np.load(tmp_path / "b" / "image.npy"), np.load(tmp_path / "b" / "image_index.npy")
+    assert sub.dtype == np.float32 and idx.dtype == np.float64 and sub.nbytes + idx.nbytes <= 4800
+    assert len(idx) == 200 and len(np.unique(idx)) == 200 and np.array_equal(sub, img.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "image_index.npy"))
+    assert bench.DUMP_MAX_BYTES + 8 <= 64_000_000
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.no_cpu_baseline and a.no_compare_numerics and a.no_other_walk and a.no_parity
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--no-parity", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.dump_outputs == "x" and a.no_parity and not (a.no_cpu_baseline or a.no_compare_numerics or a.no_other_walk)
 
 
 def _lin_program(mrt, sid, rewritten):

@@ -9,7 +9,7 @@ for tag in intree ${LIBS:-}; do
   for cfg in $CFGS; do
     IFS=, read sid W H S <<< "$cfg"
     lib=""; [ "$tag" != intree ] && lib="exp/libmrt_$tag.so"
-    MRT_EXPERIMENT_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-compare-numerics --no-other-walk --steps 3 --warmup 1 \
+    MRT_EXPERIMENT_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-compare-numerics --no-other-walk --steps 3 --warmup 1 \
         --scene $sid --width $W --height $H --samples $S > gpurun_out/ab_${tag}_$sid.log 2>&1 || exit 3
     python tools/show_bench.py gpurun_out/ab_${tag}_$sid.log "$tag scene $sid"
   done

@@ -8,7 +8,7 @@ CFGS=${CFGS:-"5,500,500,1024 9,800,800,4096 8,1024,1024,2048 7,2048,2048,8192"}
 for cfg in $CFGS; do
   IFS=, read sid W H S <<< "$cfg"
   echo "== scene $sid ${W}x${H} ${S}spp $(date +%T)"
-  timeout -k 10 400 python bench.py --no-cpu-baseline --steps 1 --warmup 0 --kernel-reps 1 \
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline --steps 1 --warmup 0 --kernel-reps 1 \
       --scene $sid --width $W --height $H --samples $S > gpurun_out/cfg_$sid.log 2>&1 || exit 3
   python tools/show_bench.py gpurun_out/cfg_$sid.log "scene $sid"
 done

@@ -36,5 +36,5 @@ fi
 step parity 600 python tools/parity_record.py --out gpurun_out/profiles/${TAG}_parity.json
 step configs 900 bash tools/configs.sh
 CFGS="1,0 2,0 2,1 4,0 4,1 4,2 4,3 8,0 8,1 8,2 8,3 8,4 8,5 8,6 8,7" STEPS=60 step scale 900 bash tools/scale_rehearsal.sh
-step bench 600 python bench.py --steps 20 --warmup 5
+step bench 600 python bench.py --full --steps 20 --warmup 5
 exit 0

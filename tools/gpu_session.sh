@@ -16,7 +16,7 @@ step() {  # name timeout cmd...
 }
 [ "${SKIP_SMOKE:-0}" = 1 ] || step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 [ "${SKIP_TESTS:-0}" = 1 ] || step gpu_tests 900 python -u -m pytest ${TESTS:-tests/} -x -v -m gpu --timeout 300 --timeout-method thread
-[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python bench.py ${BENCH_ARGS:-}
+[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python bench.py --full ${BENCH_ARGS:-}
 [ "${SKIP_PROF:-0}" = 1 ] || step prof 900 bash tools/profile.sh
 [ "${PROF_CFG:-0}" = 1 ] && step prof_cfg 1200 bash tools/prof_configs.sh
 exit 0

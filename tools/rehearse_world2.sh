@@ -6,7 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for be in nccl gloo; do
-  MRT_SAME_GPU=1 MRT_DIST_BACKEND=$be timeout -k 10 150 python bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline \
+  MRT_SAME_GPU=1 MRT_DIST_BACKEND=$be timeout -k 10 150 python bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline \
       --no-other-walk --no-compare-numerics --verify > gpurun_out/world2_$be.log 2>&1
   rc=$?
   echo "$be rc=$rc" | tee -a gpurun_out/world2_rc.txt
