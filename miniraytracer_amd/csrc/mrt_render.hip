@@ -659,18 +659,83 @@ static uint32_t scene_features(const mrt_scene_view* v, const std::vector<mrt_no
     if (v->biased != MRT_NONE) {
         f |= FT_BIASED;
         const mrt_node& b = nodes[v->biased];
-        if ((b.kind & 0xFF) == MRT_K_SPHERE) f |= FT_BSPHERE;
+        // any leaf but an xz_rect: spheres, and kinds without a pdf of their own (mrt_shade.h predraw_ok)
+        if ((b.kind & 0xFF) != MRT_K_XZ && (b.kind & 0xFF) != MRT_K_LIST) f |= FT_BSPHERE;
         if ((b.kind & 0xFF) == MRT_K_LIST)
             for (uint32_t i = 0; i < b.b; i++)
-                if ((nodes[v->children[b.a + i]].kind & 0xFF) == MRT_K_SPHERE) f |= FT_BSPHERE;
+                if ((nodes[v->children[b.a + i]].kind & 0xFF) != MRT_K_XZ) f |= FT_BSPHERE;
     }
     return f;
+}
+
+// Every index a view's records hold, against the array it points into: the table builder below and
+// both backends' walks dereference them unchecked.  Returns what is out of range ("" if nothing is);
+// runs before anything else reads the arrays and before any HIP call.
+static std::string view_range_error(const mrt_scene_view* v) {
+    auto at = [](const char* what, uint32_t i) { return std::string(what) + " (record " + std::to_string(i) + ")"; };
+    if ((v->n_nodes && !v->nodes) || (v->n_children && !v->children) || (v->n_mesh_nodes && !v->mesh_nodes) ||
+        (v->n_tris && (!v->tri_geo || !v->tri_nrm)) || (v->n_materials && !v->materials) || (v->n_textures && !v->textures) ||
+        (v->n_texels && !v->texels) || !v->perlin_ranvec || !v->perlin_perm)
+        return "null array with a non-zero count";
+    if (v->biased != MRT_NONE && v->biased >= v->n_nodes) return "bad biased node";
+    for (uint32_t i = 0; i < v->n_nodes; i++) {
+        const mrt_node& n = v->nodes[i];
+        switch (n.kind & 0xFF) {
+        case MRT_K_LIST:
+            if ((uint64_t)n.a + n.b > v->n_children) return at("object_list children run beyond n_children", i);
+            for (uint32_t c = 0; c < n.b; c++)
+                if (v->children[n.a + c] >= v->n_nodes) return at("object_list child index beyond n_nodes", i);
+            break;
+        case MRT_K_BVH:
+            if (n.a >= v->n_nodes || n.b >= v->n_nodes) return at("bvh_node child index beyond n_nodes", i);
+            break;
+        case MRT_K_MESH:
+            if (n.a >= v->n_mesh_nodes) return at("mesh root beyond n_mesh_nodes", i);
+            if (n.mat >= v->n_materials) return at("mesh material index beyond n_materials", i);
+            break;
+        case MRT_K_TRANSLATE: case MRT_K_ROTY:
+            if (n.a >= v->n_nodes) return at("instance child index beyond n_nodes", i);
+            break;
+        case MRT_K_SPHERE: case MRT_K_XY: case MRT_K_XZ: case MRT_K_YZ:
+            if (n.mat >= v->n_materials) return at("primitive material index beyond n_materials", i);
+            break;
+        case MRT_K_VOLUME:
+            if (n.a >= v->n_nodes) return at("constant_volume boundary index beyond n_nodes", i);
+            if (n.mat >= v->n_materials) return at("constant_volume material index beyond n_materials", i);
+            break;
+        default: break;  // (an unknown kind is refused where the graph reaches it: GraphCheck)
+        }
+    }
+    for (uint32_t i = 0; i < v->n_mesh_nodes; i++) {
+        const mrt_mesh_node& m = v->mesh_nodes[i];
+        const uint32_t cnt = m.count_order & 0xFFFFFFu;
+        if (cnt == 0 ? (uint64_t)m.left_or_first + 1 >= v->n_mesh_nodes : (uint64_t)m.left_or_first + cnt > v->n_tris)
+            return at(cnt == 0 ? "mesh node children beyond n_mesh_nodes" : "mesh leaf triangles beyond n_tris", i);
+    }
+    for (uint32_t i = 0; i < v->n_materials; i++) {
+        const mrt_material& m = v->materials[i];
+        // (a dielectric has no texture: material.h:121)
+        if (m.kind != MRT_M_DIELECTRIC && m.tex >= v->n_textures) return at("material texture index beyond n_textures", i);
+    }
+    for (uint32_t i = 0; i < v->n_textures; i++) {
+        const mrt_texture& t = v->textures[i];
+        if (t.kind == MRT_T_CHECKER && (t.a >= v->n_textures || t.b >= v->n_textures))
+            return at("checker texture child index beyond n_textures", i);
+        if (t.kind == MRT_T_IMAGE && (t.b == 0 || t.c == 0 || (uint64_t)t.b * t.c > (1ull << 40) ||
+                                      (uint64_t)t.a + (uint64_t)t.b * t.c * 3u > v->n_texels))
+            return at("image texture texels beyond n_texels", i);
+    }
+    return "";
 }
 
 // The scene's device tables (mrt_tables.h), built on the host from the caller's view; both
 // backends run on them: mrt_scene_upload copies them to HBM, mrt_cpu_scene_create keeps them.
 mrt_status mrt_internal_scene_tables(const mrt_scene_view* v, SceneTables* T) {
     if (!v || !T || v->root >= v->n_nodes) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_scene_upload: bad view");
+    {
+        const std::string bad = view_range_error(v);
+        if (!bad.empty()) return mrt_internal_fail(MRT_ERR_INVALID, ("mrt_scene_upload: " + bad).c_str());
+    }
     // device node table: NEEDUV flags; translate(rotate_y(x)) fused into one instance node
     std::vector<mrt_node> nodes(v->nodes, v->nodes + v->n_nodes);
     for (mrt_node& n : nodes) {
@@ -928,6 +993,8 @@ mrt_status mrt_internal_scene_tables(const mrt_scene_view* v, SceneTables* T) {
             bleaf.push_back(b);
         }
     }
+    for (const mrt_node& l : bleaf)
+        if ((l.kind & 0xFF) != MRT_K_XZ && (l.kind & 0xFF) != MRT_K_SPHERE) T->blazy = 1;
     if (bleaf.empty()) bleaf.push_back(mrt_node{});
     LinCompiler lc{nodes, v, {}};
     const char* force_generic = getenv("MRT_FORCE_GENERIC");  // test hook: run the generic machine
@@ -995,6 +1062,7 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
     S.nbleaf_f = (float)T.nbleaf;
     S.inv_nbleaf = 1.0f / S.nbleaf_f;
     S.blist = T.blist;
+    S.blazy = T.blazy;
     UP(v->textures, v->n_textures, &S.texs);
     UP((const float4*)v->perlin_ranvec, 256, &S.ranvec);
     UP(v->perlin_perm, 768, &S.perm);

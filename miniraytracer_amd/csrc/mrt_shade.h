@@ -191,6 +191,19 @@ MRT_DFN f3 biased_pdf_generate(const DScene& S, f3 origin, float time, Pcg& rng,
     return leaf_pdf_generate<F>(S, S.bleaf[i], origin, time, rng, dr);
 }
 
+// The two draws a lambertian bounce batches ahead of the mix (shade_hit): exact only when the side
+// taken consumes at least two.  cosine_pdf, xz_rect and sphere do; an object without a
+// pdf_generate of its own (scene_object.h:27-29: rects other than xz, meshes, instances, ...)
+// draws nothing, so a biased list holding one uses one draw and such a bare object none, and the
+// reference's stream (pdf.h:74-79) stands one or two draws behind a batched one for the rest of the
+// path.  Scenes with such a leaf (S.blazy, set on upload together with FT_BSPHERE, so only the
+// catch-all kernels compile this) draw the light side one by one instead.
+template <uint32_t F>
+MRT_DFN bool predraw_ok(const DScene& S, bool light) {
+    if constexpr ((F & FT_BSPHERE) != 0) return !(S.blazy != 0 && light);
+    return true;
+}
+
 // A light sample is rounding-critical (tolerance contract, DESIGN.md section 2 "Non-finite
 // samples") where xz_rect::pdf_value (rect.cpp:92-102) can return a non-finite or zero pdf on one
 // side of a last-bit difference, which main.cpp:162-164 turns into a doubling of the pixel's
@@ -451,9 +464,10 @@ MRT_DFN bool shade_hit(const DScene& S, PathState& ps, uint32_t max_bounces, con
     const f3 att = mat_color<F>(S, M, rec);
     f3 gen;
     const bool light = ((F & FT_BIASED) && S.biased != MRT_NONE) && randf(ps.rng) < 0.5f;
-    // both sides of the mix start with two draws when the surface side is cosine sampling
+    // both sides of the mix start with two draws when the surface side is cosine sampling -- unless
+    // the light side may draw fewer (predraw_ok)
     Draws dr{0.0f, 0.0f, 2u};
-    if (lamb) {
+    if (lamb && predraw_ok<F>(S, light)) {
         dr.v0 = randf(ps.rng);
         dr.v1 = randf(ps.rng);
         dr.used = 0;
@@ -621,7 +635,7 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     BSTAT(6);
     const bool light = ((F & FT_BIASED) && S.biased != MRT_NONE) && randf(ps.rng) < 0.5f;
     Draws dr{0.0f, 0.0f, 2u};
-    if (lamb) {
+    if (lamb && predraw_ok<F>(S, light)) {
         dr.v0 = randf(ps.rng);
         dr.v1 = randf(ps.rng);
         dr.used = 0;

@@ -230,7 +230,9 @@ inline std::vector<LinOp> lin_rewrite_fast(const std::vector<LinOp>& prog) {
     at[n] = (uint32_t)out.size();
     for (LinOp& o : out) {
         const uint32_t op = o.code & 0xFFu;
-        if ((op == LOP_LIST || op == LOP_INST || op == LOP_INST_END) && o.skip <= n) o.skip = at[o.skip];
+        // (a volume's skip is an op index only when it carries a sub-program: just past it)
+        const bool vsub = op == LOP_VOLUME && ((o.code >> 16) & MRT_F_VSUB) != 0;
+        if ((op == LOP_LIST || op == LOP_INST || op == LOP_INST_END || vsub) && o.skip <= n) o.skip = at[o.skip];
     }
     // MRT_F_LAST on the op the interpreter leaves for the END op (the room op steps over its data op,
     // a one-step box instance or box.h list over its body): the walk ends there without one more

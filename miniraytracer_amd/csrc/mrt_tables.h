@@ -14,6 +14,7 @@ struct SceneTables {
     std::vector<mrtd::DMat> dmats;      // materials (+ inline constant colour, dielectric quotients)
     std::vector<mrt_node> bleaf;        // leaves of scene.biased_objects
     uint32_t blist = 0, nbleaf = 1;
+    uint32_t blazy = 0;                 // a biased leaf that is neither xz_rect nor sphere (mrt_shade.h predraw_ok)
     std::vector<mrtd::LinOp> prog;      // linear hit program (empty + LOP_END when the graph has none)
     std::vector<mrtd::LinOp> prog_fast; // its tolerance-contract rewrite (lin_rewrite_fast: rooms, box.h lists)
     uint32_t prog_ops = 0;

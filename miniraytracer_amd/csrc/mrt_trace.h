@@ -165,6 +165,7 @@ struct DScene {
                                          // scalars (converted on the device they held two VGPRs, spilled)
     uint32_t root, biased, sky;
     mrt_camera cam;
+    uint32_t blazy;  // a biased leaf without a pdf_generate of its own: no batched draws (mrt_shade.h predraw_ok)
     const mrt_camera* __restrict__ camp;  // the camera in HBM, read at each path start (scalar loads)
 };
 
@@ -193,7 +194,7 @@ enum : uint32_t {
     FT_ISO = 1u << 6,      // isotropic phase function
     FT_MOVING = 1u << 7,   // moving spheres
     FT_SKY = 1u << 8,
-    FT_BSPHERE = 1u << 9,  // sphere in the biased (light-sampling) list
+    FT_BSPHERE = 1u << 9,  // a leaf other than an xz_rect in the biased (light-sampling) list
     FT_UV = 1u << 10,      // uv sampled on spheres / rects
     FT_LIN = 1u << 11,     // scene graph compiled to a linear hit program (mrt_lin.h)
     FT_BVHW = 1u << 12,    // bvh_node subtrees as wide nodes (MRT_K_BVHW)

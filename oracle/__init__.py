@@ -46,6 +46,8 @@ def lib():
         L.oracle_render_ref_order.restype = C.c_uint64
         L.oracle_pcg_stream.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]
         L.oracle_samplers.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.oracle_pdf.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]
         _lib = L
     return _lib
 
@@ -95,6 +97,18 @@ def samplers(st, sq, n, which):
     out = np.zeros((n, 3), dtype=np.float32)
     lib().oracle_samplers(st, sq, n, which, out.ctypes.data)
     return out
+
+
+def pdf(scene, node, rows, states, seq):
+    """Object pdfs of `node`: rows [n, 7] = (origin, unit dir, time) -> (pdf_value [n], pdf_generate
+    [n, 3] drawn on the streams (states[i], seq), the streams' next rand32 [n])."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    states = np.ascontiguousarray(states, dtype=np.uint64)
+    n = len(rows)
+    value, gen, nxt = np.zeros(n, dtype=np.float32), np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.uint32)
+    lib().oracle_pdf(C.byref(scene.view), int(node), n, rows.ctypes.data, states.ctypes.data, int(seq), value.ctypes.data,
+                     gen.ctypes.data, nxt.ctypes.data)
+    return value, gen, nxt
 
 
 # ---- the reference binary (oracle/_ref) ----

@@ -881,3 +881,21 @@ void oracle_samplers(uint64_t st, uint64_t sq, uint32_t n, uint32_t which, float
         out[i * 3 + 0] = p.x; out[i * 3 + 1] = p.y; out[i * 3 + 2] = p.z;
     }
 }
+
+/* Known-answer entry for the object pdfs (tests/golden/kat_pdf.npz, harness --h-mode pdf): for row
+ * i, pdf_value of node `id` for in[i] = (origin xyz, unit dir xyz, time), and pdf_generate from
+ * that origin and time on the stream (state[i], seq) followed by the stream's next rand32 (which
+ * pins how many draws the generate took). */
+void oracle_pdf(const mrt_scene_view* v, uint32_t id, uint32_t n, const float* in, const uint64_t* state, uint64_t seq,
+                float* value, float* gen, uint32_t* next) {
+    ctx C;
+    C.v = v;
+    for (uint32_t i = 0; i < n; i++) {
+        const float* r = in + (size_t)i * 7;
+        value[i] = obj_pdf_value(&C, id, ld(r), ld(r + 3), r[6]);
+        pcg_srandom(&C.rng, state[i], seq);
+        V g = obj_pdf_generate(&C, id, ld(r), r[6]);
+        gen[i * 3 + 0] = g.x; gen[i * 3 + 1] = g.y; gen[i * 3 + 2] = g.z;
+        next[i] = pcg_next(&C.rng);
+    }
+}

@@ -16,6 +16,7 @@
 //   --h-mode kat       PCG / sampler known-answer vectors (pcg.cpp).
 //   --h-mode scene     dump the scene graph select_scene() builds (types, parameters as float
 //                      bits, BVH topology incl. node_order) and the camera.
+//   --h-mode pdf       object pdf KATs: pdf_value / pdf_generate of spheres, rects and object_lists.
 //   --h-mode hits      closest-hit KATs: seeded random rays against scene.objects->hit().
 //
 // The reference's platform layer (SDL / GDI) is not compiled; the MRT_* entry points declared in
@@ -478,6 +479,60 @@ static int mode_hits(int argc, char** argv) {
     return 0;
 }
 
+// Object pdfs (scene_object.h:24-29, 64-77; rect.cpp:92-107; sphere.cpp:63-78) on objects built
+// here: a static and a moving sphere, an xz_rect (light-like, facing down), an xy_rect (no pdf of
+// its own), object_lists of two and three of them.  Row i: origin (every fourth inside the static
+// sphere), unit direction (every other one aimed at the object by its own pdf_generate), time.
+// Per object: pdf_value; pdf_generate on the stream (1000 + i, 77) and the stream's next rand32.
+static int mode_pdf(int argc, char** argv) {
+    int n = atoi(harg(argc, argv, "--h-n", "512"));
+    const char* out = harg(argc, argv, "--h-out", "pdf");
+    // kind (MRT_K_*: 6 sphere, 7 xy, 8 xz) + the node's f[0..8]
+    static const float P[4][10] = {{6, 190, 90, 190, 190, 90, 190, 0, 0, 90},
+                                   {6, 100, 200, 300, 120, 260, 290, 0, 1, 50},
+                                   {8, 213, 343, 227, 332, 554, -1, 0, 0, 0},
+                                   {7, 100, 300, 150, 400, 555, 1, 0, 0, 0}};
+    lambertian mat(new color_tex(Vec3(0.5f, 0.5f, 0.5f)));
+    scene_object* prim[4] = {
+        new sphere(Vec3(P[0][1], P[0][2], P[0][3]), P[0][9], &mat),
+        new sphere(Vec3(P[1][1], P[1][2], P[1][3]), P[1][9], &mat, Vec3(P[1][4], P[1][5], P[1][6]), P[1][7], P[1][8]),
+        new xz_rect(P[2][2], P[2][1], P[2][3], P[2][4], P[2][5], &mat),  // x0 > x1: normal_sign -1
+        new xy_rect(P[3][1], P[3][2], P[3][3], P[3][4], P[3][5], &mat)};
+    scene_object* l2[2] = {prim[2], prim[0]};
+    scene_object* l3[3] = {prim[3], prim[1], prim[2]};
+    scene_object* obj[6] = {prim[0], prim[1], prim[2], prim[3], new object_list<scene_object>(l2, 2, 0.0f, 1.0f),
+                            new object_list<scene_object>(l3, 3, 0.0f, 1.0f)};
+    std::vector<float> rows((size_t)n * 7), value((size_t)n * 6), gen((size_t)n * 6 * 3);
+    std::vector<uint32_t> next((size_t)n * 6);
+    for (int i = 0; i < n; i++) {
+        Init_Thread_RNG(424242 + (uint64_t)i, 99);  // input stream
+        Vec3 o = (i % 4 == 0) ? Vec3(P[0][1], P[0][2], P[0][3]) + (0.95f * P[0][9]) * random_in_sphere()
+                              : Vec3(randf() * 555.f, randf() * 555.f, randf() * 555.f);
+        float tm = randf();
+        Vec3 d = random_in_sphere();
+        if (i % 2 == 1) d = obj[(i / 2) % 6]->pdf_generate(o, tm);
+        ray r(o, d, tm, 0);  // (normalizes dir, as the scattered ray mix_pdf::value is asked about)
+        float* q = &rows[(size_t)i * 7];
+        q[0] = o.x; q[1] = o.y; q[2] = o.z; q[3] = r.dir.x; q[4] = r.dir.y; q[5] = r.dir.z; q[6] = tm;
+        for (int k = 0; k < 6; k++) {
+            value[(size_t)i * 6 + k] = obj[k]->pdf_value(o, r.dir, tm);
+            Init_Thread_RNG(1000 + (uint64_t)i, 77);
+            Vec3 g = obj[k]->pdf_generate(o, tm);
+            float* gq = &gen[((size_t)i * 6 + k) * 3];
+            gq[0] = g.x; gq[1] = g.y; gq[2] = g.z;
+            next[(size_t)i * 6 + k] = rand32();
+        }
+    }
+    std::string b(out);
+    write_npy((b + "_prims.npy").c_str(), "<f4", {4, 10}, P, sizeof P);
+    write_npy((b + "_rows.npy").c_str(), "<f4", {(size_t)n, 7}, rows.data(), rows.size() * 4);
+    write_npy((b + "_value.npy").c_str(), "<f4", {(size_t)n, 6}, value.data(), value.size() * 4);
+    write_npy((b + "_gen.npy").c_str(), "<f4", {(size_t)n, 6, 3}, gen.data(), gen.size() * 4);
+    write_npy((b + "_next.npy").c_str(), "<u4", {(size_t)n, 6}, next.data(), next.size() * 4);
+    printf("{\"n\":%d,\"lists\":[[2,0],[3,1,2]],\"state0\":1000,\"seq\":77}\n", n);
+    return 0;
+}
+
 static int mode_stream(int argc, char** argv) {
     MRT_Params* p = getParams();
     uint64_t seed = strtoull(harg(argc, argv, "--h-seed", "11350390909718046443"), nullptr, 0);
@@ -622,6 +677,7 @@ int main(int argc, char** argv) {
     H_objdir = harg(argc, argv, "--h-objdir", "../obj");
     if (!strcmp(mode, "kat")) return mode_kat(argc, argv);
     if (!strcmp(mode, "texels")) return mode_texels(argc, argv);
+    if (!strcmp(mode, "pdf")) return mode_pdf(argc, argv);
     ParseArgv(argc, argv);
     if (!strcmp(mode, "scene")) return mode_scene(argc, argv);
     if (!strcmp(mode, "hits")) return mode_hits(argc, argv);

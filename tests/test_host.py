@@ -408,3 +408,66 @@ def test_volume_boundary_subprogram_structure(mrt):
     c7, _ = _lin_program(mrt, 7, False)
     v7 = [i for i, o in enumerate(c7 & 0xFF) if o == VOLUME]
     assert v7 and all(not ((c7[i] >> 16) & VSUB) and (c7[i + 1] & 0xFF) == 9 for i in v7)
+
+
+# Malformed views, each a few statements run on a copy `s` of a reference scene's view
+# (tests/synth_scenes.py) before the upload; (base scene, statements, what the refusal must name).
+MALFORMED = {
+    # index ranges mrt_scene_upload checks before it dereferences anything
+    "list_run_past_children": (5, "s.nodes[0]['b'] = 1000", "children run beyond n_children"),
+    "list_run_wraps_uint32": (5, "s.nodes[0]['a'] = 0xFFFFFFF8; s.nodes[0]['b'] = 0x10", "children run beyond n_children"),
+    "list_child_past_nodes": (5, "s.children[int(s.nodes[0]['a'])] = 9999", "child index beyond n_nodes"),
+    "biased_child_past_nodes": (5, "s.children[int(s.nodes[s.biased]['a'])] = 9999", "child index beyond n_nodes"),
+    "biased_past_nodes": (5, "s.biased = 9999", "bad biased node"),
+    "volume_boundary_past_nodes": (6, "s.nodes[7]['a'] = 9999", "constant_volume boundary index beyond n_nodes"),
+    "instance_child_past_nodes": (5, "s.nodes[8]['a'] = 9999", "instance child index beyond n_nodes"),
+    "bvh_child_past_nodes": (0, "s.nodes[s.root]['b'] = 99999", "bvh_node child index beyond n_nodes"),
+    "primitive_mat_past_materials": (5, "s.nodes[1]['mat'] = 77", "primitive material index beyond n_materials"),
+    "mesh_mat_past_materials": (9, "s.nodes[7]['mat'] = 77", "mesh material index beyond n_materials"),
+    "volume_mat_past_materials": (6, "s.nodes[7]['mat'] = 77", "constant_volume material index beyond n_materials"),
+    "material_tex_past_textures": (5, "s.materials[0]['tex'] = 77", "material texture index beyond n_textures"),
+    "checker_child_past_textures": (5, "s.materials[0]['tex'] = s.texture(ss.T_CHECKER, a=0, b=77, f=(1.0,))",
+                                    "checker texture child index beyond n_textures"),
+    "mesh_leaf_past_tris": (9, "i = int(np.nonzero(s.mesh_nodes['count_order'] & 0xFFFFFF)[0][0]); "
+                               "s.mesh_nodes[i]['left_or_first'] = len(s.tri_geo)", "mesh leaf triangles beyond n_tris"),
+    "mesh_root_past_mesh_nodes": (9, "s.nodes[7]['a'] = 1 << 20", "mesh root beyond n_mesh_nodes"),
+    "image_texels_past_texels": (5, "s.materials[0]['tex'] = s.texture(ss.T_IMAGE, a=0, b=100, c=100)",
+                                 "image texture texels beyond n_texels"),
+    # refused before this check existed
+    "cycle": (5, "s.children[int(s.nodes[0]['a'])] = 0", "cyclic scene graph"),
+    "nested_volume": (6, "s.nodes[7]['a'] = 17", "nested constant_volume"),
+    "unknown_kind": (5, "s.nodes[1]['kind'] = 99", "unknown node kind"),
+    "bad_root": (5, "s.root = 9999", "bad view"),
+    "nested_biased_list": (5, "s.biased = s.list([s.list([3])])", "nested biased object_list"),
+    "mesh_leaf_above_127": (9, "i = int(np.nonzero(s.mesh_nodes['count_order'] & 0xFFFFFF)[0][0]); "
+                               "s.mesh_nodes[i]['left_or_first'] = 0; s.mesh_nodes[i]['count_order'] = 200", "mesh BVH outside the device encoding"),
+}
+_MALFORMED_PRELUDE = """
+import sys
+sys.path[:0] = [{root!r}, {tests!r}]
+import numpy as np
+import miniraytracer_amd as mrt
+import synth_scenes as ss
+s = ss.Synth(mrt.select_scene({sid}, 1.0))
+{code}
+s._view = None
+try:
+    mrt.Renderer(s, "cpu")  # MRT_DEVICE_CPU: the same host check, and no GPU ever sees the view
+    print("ACCEPTED")
+except mrt.MrtError as e:
+    print("REFUSED:", e)
+"""
+
+
+@pytest.mark.parametrize("name", list(MALFORMED))
+def test_upload_refuses_malformed_view(name):
+    """mrt_scene_upload refuses a view whose records point outside its arrays with MRT_ERR_INVALID
+    and a message naming what is out of range, before reading through the index.  One process per
+    view (an unchecked index crashes the host), CPU device only, upload only."""
+    import subprocess
+    import sys
+    sid, code, what = MALFORMED[name]
+    src = _MALFORMED_PRELUDE.format(root=ROOT, tests=os.path.join(ROOT, "tests"), sid=sid, code=code)
+    r = subprocess.run([sys.executable, "-c", src], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.returncode, r.stderr[-500:])
+    assert r.stdout.startswith("REFUSED:") and "invalid argument" in r.stdout and what in r.stdout, r.stdout

@@ -132,3 +132,40 @@ def test_oracle_reproduces_reference_threads1_mode(mrt, orc, sid, mode):
     img, r = orc.render_ref_order(sc, orc.desc(w, h, spp, depth=depth, mode=mode), tile_size=ts)
     assert r == rays
     assert np.array_equal(img[..., :3].view(np.uint32), g["image"].view(np.uint32))
+
+
+def test_oracle_pdfs_match_reference(mrt, orc):
+    """The restatement's object pdfs (obj_pdf_value / obj_pdf_generate: sphere, moving sphere,
+    xz_rect, the default of scene_object.h:24-29 for an xy_rect, object_lists of two and three)
+    against the reference's own classes (tests/golden/kat_pdf.npz, harness --h-mode pdf): pdf_value
+    bits for seeded (origin, dir, time) rows -- origins inside the sphere and directions that miss
+    included -- and pdf_generate's vector plus the stream's next rand32, which pins the draw count.
+    No reference scene exercises these paths; the synthetic catalogue relies on them."""
+    import synth_scenes as ss
+    g = np.load(os.path.join(GOLDEN, "kat_pdf.npz"))
+    s = ss.Synth(mrt.select_scene(5, 1.0)).clear()
+    mat = s.lambertian(0.5, 0.5, 0.5)
+    prim = []
+    for p in g["prims"]:
+        kind, f = int(p[0]), p[1:]
+        if kind == ss.K_SPHERE:
+            moving = f[7] - f[6] > np.finfo(np.float32).eps  # sphere.h:21
+            prim.append(s.node(kind, mat=mat, f=f, flags=ss.F_MOVING if moving else 0))
+        else:
+            prim.append(s.node(kind, mat=mat, f=f[:6]))
+    objs = prim + [s.list([prim[i] for i in g["list2"]]), s.list([prim[i] for i in g["list3"]])]
+    s.root = objs[-1]
+    rows, n = g["rows"], len(g["rows"])
+    state0, seq = (int(x) for x in g["stream"])
+    states = np.arange(n, dtype=np.uint64) + np.uint64(state0)
+    assert (np.linalg.norm(rows[::4, :3] - g["prims"][0][1:4], axis=1) < g["prims"][0][9]).all()  # origins inside the sphere
+    for k, node in enumerate(objs):
+        value, gen, nxt = orc.pdf(s, node, rows, states, seq)
+        want = g["value"][:, k]
+        if k == 3:  # the xy_rect has no pdf of its own
+            assert (want == 0).all()
+        else:  # the rows hold hits and misses of every other object
+            assert (want == 0).any() and (want != 0).any(), k
+        assert np.array_equal(value.view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), f"pdf_value of object {k}"
+        assert np.array_equal(gen.view(np.uint32), np.ascontiguousarray(g["gen"][:, k]).view(np.uint32)), f"pdf_generate of object {k}"
+        assert np.array_equal(nxt, g["next"][:, k]), f"draw count of object {k}"

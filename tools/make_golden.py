@@ -5,6 +5,7 @@ exists; the GPU box only reads the committed fixtures.
 
 Fixtures (all small; data only -- inputs and expected outputs):
   kat_pcg.json            PCG32 rand32/randf and sampler outputs for fixed seeds (pcg.cpp)
+  kat_pdf.npz             pdf_value / pdf_generate of spheres, rects and object_lists (`--only-pdf`)
   scene_<id>.json.gz      scene graph dump of select_scene (camera, primitives, BVH topology)
   hits_<id>.npy           closest-hit KATs: rays vs scene.objects->hit()
   stream_<id>.npz         stream-matched render: per-path radiance + ray counts + draw() image
@@ -249,6 +250,17 @@ def main():
         kats.append(json.loads(run(EXACT, ["--h-mode", "kat", "--h-state", st, "--h-seq", sq, "--h-n", 64])))
     with open(os.path.join(OUT, "kat_pcg.json"), "w") as f:
         json.dump(kats, f)
+
+    # 1b. object pdf KATs (sphere, moving sphere, xz_rect, xy_rect, object_lists of them)
+    with tempfile.TemporaryDirectory() as tmp:
+        b = os.path.join(tmp, "pdf")
+        meta = json.loads(run(EXACT, ["--h-mode", "pdf", "--h-n", 768, "--h-out", b]))
+        np.savez_compressed(os.path.join(OUT, "kat_pdf.npz"), prims=np.load(b + "_prims.npy"), rows=np.load(b + "_rows.npy"),
+                            value=np.load(b + "_value.npy"), gen=np.load(b + "_gen.npy"), next=np.load(b + "_next.npy"),
+                            list2=np.array(meta["lists"][0]), list3=np.array(meta["lists"][1]),
+                            stream=np.array([meta["state0"], meta["seq"]], dtype=np.uint64))
+    if "--only-pdf" in sys.argv:
+        return
 
     # 2. scene dumps
     for sid, (w, h) in SCENE_SIZES.items():
