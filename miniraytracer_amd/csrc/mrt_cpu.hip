@@ -121,6 +121,7 @@ mrt_status mrt_cpu_scene_create(const mrt_scene_view* v, mrt_cpu_scene** out) {
     S.inv_nbleaf = 1.0f / S.nbleaf_f;
     S.blist = T.blist;
     S.blazy = T.blazy;
+    S.light_once = T.light_once;
     S.root = v->root;
     S.biased = v->biased;
     S.sky = v->sky;

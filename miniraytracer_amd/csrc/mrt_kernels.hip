@@ -477,6 +477,9 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
         f3 st_v{0.0f, 0.0f, 0.0f};
         uint32_t st_off = 0;  // byte offset of the path's radiance (a launch chunk is < 4 GiB)
         bool st_pend = false;
+        // Cornell fast walk: the sphere's 1 / radius, once per launch (mrt_sig.h cornell_sphere_inv_rad)
+        float sph_inv_rad = 0.0f;
+        if constexpr (kBox6Walk<F>) sph_inv_rad = cornell_sphere_inv_rad(const_ptr(S.prog));
         for (;;) {
             bool want_ray = false;
             // the next ray's arguments: written and read within one iteration (declared here, a
@@ -493,7 +496,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                         dst[2] = st_v.z;
                     }
                     st_pend = false;
-                }, CritSink{idx, kCritOff<F>});
+                }, CritSink{idx, kCritOff<F>}, sph_inv_rad);
                 PH_MARK(ph, 2);
                 if (ended) {
                     st_v = end_path(ps, lev, L);
@@ -588,6 +591,9 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             if (want_ray) {
                 BSTATC(12, pr.kind != 0);
                 ps.r = make_ray(pr.o, pr.dir, pr.time, pr.inside);
+                // the Cornell fast walk's light test, once per ray: the scatter's light pdf below and
+                // the next iteration's walk both read it (one VGPR across the back edge)
+                if constexpr (kBox6Walk<F>) ps.lt = cornell_light_t<F>(const_ptr(S.prog), ps.r);
                 PH_MARK(ph, 8);
                 if (pr.kind) finish_scatter<F, LK>(S, ps, lev, pr);
             }

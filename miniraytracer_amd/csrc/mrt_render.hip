@@ -1008,6 +1008,11 @@ mrt_status mrt_internal_scene_tables(const mrt_scene_view* v, SceneTables* T) {
     if (lin && lc.vsub) T->features |= FT_VSUB;
     if (lin) cornell_room_fill(lc.prog.data(), (uint32_t)lc.prog.size());  // (Cornell shape: the room into the END op)
     if (lin && !(no_sig && *no_sig && *no_sig != '0')) T->features |= MRT_SIG_BITS(lin_sig_of(lc.prog.data(), (uint32_t)lc.prog.size()));
+    // the Cornell walk tests op 3 (the light) once per ray; the same test serves xz_rect::pdf_value where
+    // the biased list is that one rect: same bounds, plane and side, bit for bit
+    T->light_once = (lin && MRT_SIG_OF(T->features) == SIG_CORNELL && v->biased != MRT_NONE && bleaf.size() == 1 &&
+                     (bleaf[0].kind & 0xFF) == MRT_K_XZ && memcmp(bleaf[0].f, lc.prog[3].f, 6 * sizeof(float)) == 0)
+                        ? 1u : 0u;
     T->nbleaf = blist ? nodes[v->biased].b : 1u;
     T->blist = blist;
     T->max_frames = gc.max_frames;
@@ -1063,6 +1068,7 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
     S.inv_nbleaf = 1.0f / S.nbleaf_f;
     S.blist = T.blist;
     S.blazy = T.blazy;
+    S.light_once = T.light_once;
     UP(v->textures, v->n_textures, &S.texs);
     UP((const float4*)v->perlin_ranvec, 256, &S.ranvec);
     UP(v->perlin_perm, 768, &S.perm);

@@ -107,6 +107,15 @@ struct Draws {
 
 // biased object pdfs: object_list / xz_rect / sphere pdf_value & pdf_generate
 // (scene_object.h:64-77, rect.cpp:92-107, sphere.cpp:63-78, scene_object.h:24-29)
+// xz_rect::pdf_value (rect.cpp:92-102) from its hit test's outcome: the rect's bounds f[0..3] and
+// side f[5], the ray's unit direction, the hit's t
+MRT_DFN float xz_pdf_of_hit(const float* f, f3 dir, bool h, float t) {
+    const float area = (f[1] - f[0]) * (f[3] - f[2]);
+    const float dist_sq = t * t;
+    const float cosine = fabsf(dot(dir, f3{0, f[5], 0}));
+    const float pdf = dist_sq / (cosine * area);
+    return h ? pdf : 0.0f;
+}
 template <uint32_t F>
 MRT_DFN float leaf_pdf_value(const DScene& S, const mrt_node& n, f3 origin, f3 dir, float time) {
     uint32_t k = MRT_NODE_KIND(n);
@@ -115,11 +124,7 @@ MRT_DFN float leaf_pdf_value(const DScene& S, const mrt_node& n, f3 origin, f3 d
         const Ray r = make_ray_unit<kFastUnit<F>>(origin, dir, 0.0f, 0);  // dir: the scattered ray's unit direction
         float t;
         const bool h = lin_prim_t<F, MRT_K_XZ>(n, r, 0.001f, FLT_MAX_, &t);
-        const float area = (n.f[1] - n.f[0]) * (n.f[3] - n.f[2]);
-        const float dist_sq = t * t;
-        const float cosine = fabsf(dot(dir, f3{0, n.f[5], 0}));
-        const float pdf = dist_sq / (cosine * area);
-        return h ? pdf : 0.0f;
+        return xz_pdf_of_hit(n.f, dir, h, t);
     }
     if ((F & FT_BSPHERE) && k == MRT_K_SPHERE) {
         Ray r = make_ray_unit<kFastUnit<F>>(origin, dir, time, 0);
@@ -284,6 +289,7 @@ struct PathState {
 #if MRT_FWD_FOLD
     f3 T;            // throughput of the bounces so far (forward fold)
 #endif
+    float lt;        // Cornell fast walk: the light's t on ray r, or a miss (mrt_sig.h cornell_light_t)
 };
 static constexpr uint32_t LEV_LOUD = 0x80000000u;
 
@@ -503,7 +509,9 @@ MRT_DFN bool trace_segment(const DScene& S, PathState& ps, uint32_t max_bounces,
                                               const LStack& Ls, f3* L, PhaseClock& ph, const CritSink& cs = CritSink{0u, 0u}) {
     HitRec rec;
     bool hit;
-    if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, ps.r, 0.001f, rec, Ls);
+    if constexpr (kBox6Walk<F>)
+        hit = scene_hit_sig<F>(S, ps.r, kCornellTmin, rec, Ls, cornell_light_t<F>(const_ptr(S.prog), ps.r), cornell_sphere_inv_rad(const_ptr(S.prog)));
+    else if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, ps.r, 0.001f, rec, Ls);
     else if constexpr ((F & FT_LIN) != 0) hit = scene_hit_lin<F>(S, ps.r, 0.001f, rec, Ls, ps.rng, ph);
     else hit = scene_hit<F>(S, ps.r, 0.001f, rec, ps.rng, Ls);
     PH_MARK(ph, 1);
@@ -563,14 +571,16 @@ MRT_DFN void dielectric_scatter(const DMat& M, const Ray& r, f3 n, Pcg& rng, Pen
 // trace_segment up to the next ray's constructor arguments.  Returns true when the path has
 // ended (radiance in *L); otherwise *pr holds the next ray's arguments.
 // `flush` runs once the hit is known, before the material is read (the path loop issues the
-// previous path's radiance store there).
+// previous path's radiance store there).  inv_rad: kBox6Walk kernels' cornell_sphere_inv_rad.
 template <uint32_t F, uint32_t LK, typename FLUSH>
 MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, const LevStore<LK>& lev,
-                                            const LStack& Ls, f3* L, PendRay* pr, PhaseClock& ph, FLUSH&& flush, const CritSink& cs = CritSink{0u, 0u}) {
+                                            const LStack& Ls, f3* L, PendRay* pr, PhaseClock& ph, FLUSH&& flush, const CritSink& cs = CritSink{0u, 0u},
+                                            float inv_rad = 0.0f) {
     HitRec rec;
     Ray& r = ps.r;
     bool hit;
-    if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, r, 0.001f, rec, Ls);
+    if constexpr (kBox6Walk<F>) hit = scene_hit_sig<F>(S, r, kCornellTmin, rec, Ls, ps.lt, inv_rad);  // (ps.lt: set where the path loop makes r)
+    else if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, r, 0.001f, rec, Ls);
     else if constexpr ((F & FT_LIN) != 0) hit = scene_hit_lin<F>(S, r, 0.001f, rec, Ls, ps.rng, ph);
     else hit = scene_hit<F>(S, r, 0.001f, rec, ps.rng, Ls);
     PH_MARK(ph, 1);
@@ -664,7 +674,21 @@ MRT_DFN void finish_scatter(const DScene& S, PathState& ps, const LevStore<LK>& 
         sval = 1 / (2 * PI_F);
         spdf = 1.0f / (2.0f * PI_F);
     }
-    const float pdf_v = ((F & FT_BIASED) && S.biased != MRT_NONE) ? 0.5f * (biased_pdf_value<F>(S, sc.o, sc.d, sc.time) + sval) : sval;
+    float pdf_v = sval;
+    if ((F & FT_BIASED) && S.biased != MRT_NONE) {
+        float bv;
+        if (kBox6Walk<F> && S.light_once) {
+            // the biased list is the walk's light: xz_rect::pdf_value from the ray's one light test
+            // (ps.lt; the rect's words from op 3, the biased leaf's bit for bit)
+            const CornellRect d = cornell_load(const_ptr(S.prog)[3]);
+            const float f[6] = {__uint_as_float(d.b0), __uint_as_float(d.b1), __uint_as_float(d.b2), __uint_as_float(d.b3),
+                                __uint_as_float(d.k), __uint_as_float(d.ns)};
+            bv = xz_pdf_of_hit(f, sc.d, !(ps.lt < 0.0f), ps.lt);
+        } else {
+            bv = biased_pdf_value<F>(S, sc.o, sc.d, sc.time);
+        }
+        pdf_v = 0.5f * (bv + sval);
+    }
     const float4 lv = make_float4(pr.att.x * spdf, pr.att.y * spdf, pr.att.z * spdf, pdf_v);
     push_level(ps, lev, lv);
 }

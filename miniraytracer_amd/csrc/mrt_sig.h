@@ -525,7 +525,12 @@ MRT_DFN void cornell_room(const CornellRoom& d, const Ray& r, float tmin, Cornel
     const float t0y = (lo1 - r.o.y) * r.inv.y, t1y = (hi1 - r.o.y) * r.inv.y;
     const float t0z = (lo2 - r.o.z) * r.inv.z, t1z = (hi2 - r.o.z) * r.inv.z;
     const float fx = fmaxf(t0x, t1x), fy = fmaxf(t0y, t1y), fz = fmaxf(t0z, t1z);
-    const float tn = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
+    float tn = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z));
+#if defined(__HIP_DEVICE_COMPILE__)
+    // taken here, beside the products: sunk below sel3's asms the three mins sat in another block,
+    // where the slab values no longer count as canonical and each got a v_max x, x in front
+    asm volatile("" : "+v"(tn));
+#endif
     const float tf = fminf(fminf(fx, fy), fz);
     // the exit face: its axis (ties to the later axis: z, then y, as the later rects win), and its
     // side (the max plane when the ray goes up that axis)
@@ -592,8 +597,41 @@ MRT_DFN void cornell_rect(const CornellRect& d, const Ray& r, float tmin, Cornel
     w.ns = h ? o.f[5] : w.ns;
     w.mat = h ? d.mat : w.mat;
 }
+// The light (op 3) is tested ONCE per ray, when the ray is made: its t with the walk's tmin and no
+// upper bound, kCornellMiss for a miss.  The walk then only compares it with the room's hit
+// (cornell_rect's compare and tie rule), and a scattered ray's xz_rect::pdf_value reads its hit
+// flag and distance from it (mrt_shade.h finish_scatter, DScene::light_once) instead of testing
+// the same rect a second time.
+static constexpr float kCornellTmin = 0.001f, kCornellMiss = -1.0f;  // (a hit's t is >= tmin > 0, or NaN)
 template <uint32_t F>
-MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, float tmin, HitRec& rec) {
+MRT_DFN float cornell_light_t(const MRT_CONST_AS LinOp* prog, const Ray& r) {
+    static_assert(kSigs[SIG_CORNELL].op[3] == LOP_PRIM && kSigs[SIG_CORNELL].kind[3] == MRT_K_XZ, "Cornell shape: the light at op 3");
+    const CornellRect d = cornell_load(prog[3]);
+    LinOp o;
+    o.code = 0;  // (lin_prim_t reads the flags only under the exact contract's guards)
+    o.f[0] = __uint_as_float(d.b0);
+    o.f[1] = __uint_as_float(d.b1);
+    o.f[2] = __uint_as_float(d.b2);
+    o.f[3] = __uint_as_float(d.b3);
+    o.f[4] = __uint_as_float(d.k);
+    o.f[5] = __uint_as_float(d.ns);
+    float t;
+    const bool h = lin_prim_t<F, MRT_K_XZ>(o, r, kCornellTmin, FLT_MAX_, &t);
+    return h ? t : kCornellMiss;
+}
+// 1 / radius of the sphere (op 17) as the record's divf takes it: wave-uniform, taken once per launch
+// by the path loop and held in an SGPR instead of a v_rcp_f32 per iteration
+MRT_DFN float cornell_sphere_inv_rad(const MRT_CONST_AS LinOp* prog) {
+#if MRT_FAST_DIV && defined(__HIP_DEVICE_COMPILE__)
+    const float y = __builtin_amdgcn_rcpf(prog[17].f[8]);
+    return __uint_as_float(uniform_u32(__float_as_uint(y)));
+#else
+    (void)prog;
+    return 0.0f;  // (unused: the record divides)
+#endif
+}
+template <uint32_t F>
+MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, float tmin, float lt, float inv_rad, HitRec& rec) {
     constexpr const LinSig& G = kSigs[SIG_CORNELL];
     static_assert(G.op[7] == LOP_INST && G.kind[7] == MRT_K_TRROTY && G.op[8] == LOP_LIST && G.skip[8] == 15 &&
                       G.op[17] == LOP_PRIM && G.kind[17] == MRT_K_SPHERE,
@@ -606,7 +644,15 @@ MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, floa
     CornellRect d3 = cornell_load(prog[3]);
     cornell_take(dr, d3);
     cornell_room<F>(dr, r, tmin, w);
-    cornell_rect<F, 3>(d3, r, tmin, w);
+    {  // the light: cornell_rect<F, 3>'s outcome from the ray's one test (cornell_light_t, made with this tmin)
+        (void)tmin;
+        const bool h = !(lt < 0.0f) & !(lt > w.closest);
+        w.closest = h ? lt : w.closest;
+        w.code = h ? 2u : w.code;
+        w.k = h ? __uint_as_float(d3.k) : w.k;
+        w.ns = h ? __uint_as_float(d3.ns) : w.ns;
+        w.mat = h ? d3.mat : w.mat;
+    }
     CornellBox db = cornell_load_box(prog[7], prog[8]);
     CornellSphere dsp = cornell_load_sphere(prog[17]);
     cornell_take(db, dsp);
@@ -675,7 +721,12 @@ MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, floa
     const float lx = a == 0u ? w.ns : 0.0f, ly = a == 1u ? w.ns : 0.0f, lz = a == 2u ? w.ns : 0.0f;
     f3 n{lx, ly, lz};
     if (w.code >= 4u) n = f3{c * lx + s * lz, ly, c * lz - s * lx};  // unrotate_rec's normal
+#if MRT_FAST_DIV && defined(__HIP_DEVICE_COMPILE__)
+    if (w.code == 7u) n = mulf(sub(p, f3{so.f[0], so.f[1], so.f[2]}), inv_rad);  // divf's product, its rcp taken once
+#else
+    (void)inv_rad;
     if (w.code == 7u) n = divf(sub(p, f3{so.f[0], so.f[1], so.f[2]}), so.f[8]);
+#endif
     rec.n = n;
     return true;
 }
@@ -685,12 +736,13 @@ template <uint32_t F>
 static constexpr uint32_t kBox6Walk = (MRT_FAST_BOX && MRT_SIG_OF(F) == SIG_CORNELL && !(F & (FT_UV | FT_MOVING))) ? 1u : 0u;
 
 // scene_object::hit for a program of shape SIG (same contract as scene_hit_lin)
+// (lt, inv_rad: kBox6Walk kernels only -- cornell_light_t of r, made with this tmin; cornell_sphere_inv_rad)
 template <uint32_t F>
-MRT_DFN bool scene_hit_sig(const DScene& S, Ray& r, float tmin, HitRec& rec, const LStack& L) {
+MRT_DFN bool scene_hit_sig(const DScene& S, Ray& r, float tmin, HitRec& rec, const LStack& L, float lt = 0.0f, float inv_rad = 0.0f) {
     constexpr uint32_t SIG = MRT_SIG_OF(F);
     constexpr bool INST = (F & FT_INST) != 0;
     if constexpr (kBox6Walk<F>) {  // (the shape implies MRT_F_BOX6 on op 8: lin_sig_of)
-        return cornell_fast_hit<F>(const_ptr(S.prog), r, tmin, rec);
+        return cornell_fast_hit<F>(const_ptr(S.prog), r, tmin, lt, inv_rad, rec);
     } else {
     if (INST) lin_save_ray(L, r);
     const MRT_CONST_AS LinOp* prog = const_ptr(S.prog);

@@ -15,6 +15,7 @@ struct SceneTables {
     std::vector<mrt_node> bleaf;        // leaves of scene.biased_objects
     uint32_t blist = 0, nbleaf = 1;
     uint32_t blazy = 0;                 // a biased leaf that is neither xz_rect nor sphere (mrt_shade.h predraw_ok)
+    uint32_t light_once = 0;            // Cornell shape whose one biased leaf is op 3's rect (DScene::light_once)
     std::vector<mrtd::LinOp> prog;      // linear hit program (empty + LOP_END when the graph has none)
     std::vector<mrtd::LinOp> prog_fast; // its tolerance-contract rewrite (lin_rewrite_fast: rooms, box.h lists)
     uint32_t prog_ops = 0;

@@ -166,6 +166,9 @@ struct DScene {
     uint32_t root, biased, sky;
     mrt_camera cam;
     uint32_t blazy;  // a biased leaf without a pdf_generate of its own: no batched draws (mrt_shade.h predraw_ok)
+    // Cornell shape: the biased list is one xz_rect whose bounds, plane and side are op 3's bit for bit,
+    // so the walk's light test of a scattered ray also gives its light pdf (mrt_sig.h cornell_light_t)
+    uint32_t light_once;
     const mrt_camera* __restrict__ camp;  // the camera in HBM, read at each path start (scalar loads)
 };
 
