@@ -17,7 +17,7 @@ CSRC     = miniraytracer_amd/csrc
 OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
-           $(OBJDIR)/mrt_kernels_pex.o \
+           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_denoise.o \
            $(OBJDIR)/mrt_cpu.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
@@ -59,6 +59,18 @@ HOSTFMA ?= -mfma
 $(OBJDIR)/mrt_cpu.o: $(CSRC)/mrt_cpu.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(HOSTFMA) --offload-host-only -c $< -o $@
+
+# the first-hit feature buffers (mrt_aux_kernel<F>): the exact contract's hit code in a translation
+# unit of its own, so the path-kernel objects above do not change with it
+$(OBJDIR)/mrt_aux.o: $(CSRC)/mrt_aux.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(HIPDEV) -DMRT_FAST=0 -c $< -o $@
+
+# the a-trous filter, host and device from include/mrt_denoise.h: no contraction on either side
+# (HIPFLAGS), the host's explicit fma() as one instruction (as in the CPU backend)
+$(OBJDIR)/mrt_denoise.o: $(CSRC)/mrt_denoise.hip include/mrt_denoise.h $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(if $(HOSTFMA),-Xarch_host $(HOSTFMA)) -c $< -o $@
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)

@@ -225,6 +225,42 @@ mrt_status mrt_tonemap_argb(const float* rgb, uint32_t width, uint32_t height, u
 mrt_status mrt_lum_max_device(const float* d_rgb, uint32_t n, float* d_lwmax, void* stream);
 mrt_status mrt_tonemap_device(const float* d_rgb, uint32_t n, const float* d_lwmax, uint32_t* d_argb, void* stream);
 
+/* ---- feature buffers and denoise ---------------------------------------------------------------
+ * (an addition; the reference returns the radiance image only.)  First-hit feature buffers for a
+ * denoiser, and an edge-avoiding a-trous filter (Dammertz et al. 2010) that uses them.
+ *
+ * Per pixel, the mean over the desc's sqrt_samples^2 camera rays of the FIRST hit:
+ *   normal = (n.x, n.y, n.z, coverage), albedo = (r, g, b, depth); float4 each.
+ * Sample s of a pixel uses the render's own stream and camera ray for that (pixel, sample, spp) and
+ * one scene hit with tmin 0.001 -- the hit the render's first segment finds.  Per hit: the normal
+ * facing the ray (a miss: 0), coverage 1 (miss: 0), depth = the hit's t (miss: 0); albedo = the
+ * material's colour (lambertian, isotropic, metal), (1,1,1) (dielectric), the emitted radiance
+ * (light: 0 from the back), the miss radiance (sky or 0).  Each channel is the float32 sum over
+ * s = 0 .. ns-1 in that order, divided by (float)ns.  Read from the desc: width, height,
+ * sqrt_samples, seed, tile_size, rank, world, pixels / n_pixels; flags may be 0 or MRT_RF_FAST
+ * (accepted and ignored: the buffers always come from the exact arithmetic, so they are
+ * bit-identical on both backends); any other flag bit is MRT_ERR_INVALID. */
+mrt_status mrt_render_aux(mrt_scene* s, const mrt_render_desc* d, float* normal_out, float* albedo_out);
+        /* host W*H*4 each, owned pixels only, like mrt_render; both backends */
+mrt_status mrt_render_aux_device(mrt_scene* s, const mrt_render_desc* d, float* d_normal, float* d_albedo, void* stream);
+        /* GPU; n_local float4 each in mrt_local_pixels order; enqueued on `stream`, nothing
+           synchronised, nothing allocated once mrt_prepare ran for d (capturable) */
+
+/* The filter: `iterations` passes i = 0.. of the 5x5 B3 kernel at step 2^i, each tap weighted by
+ * normal, depth, albedo and colour agreement with the centre; sigma_color is halved every pass.
+ * The exact formulas: include/mrt_denoise.h (one source for host and device: same bits).
+ * Defaults (mrt_default_denoise_params; chosen on the Cornell box at 16 spp):
+ *   iterations 3, sigma_color 8, sigma_normal 32, sigma_albedo 0.3, sigma_depth 0.02
+ * Valid: iterations <= 16; sigma_color, sigma_albedo, sigma_depth > 0; sigma_normal >= 0. */
+typedef struct mrt_denoise_params { uint32_t iterations; float sigma_color, sigma_normal, sigma_albedo, sigma_depth; } mrt_denoise_params;
+void mrt_default_denoise_params(mrt_denoise_params* p);
+mrt_status mrt_denoise(const float* rgb, const float* normal, const float* albedo, uint32_t width, uint32_t height,
+                       const mrt_denoise_params* p, float* rgb_out);          /* host buffers, row-major W*H*4 */
+mrt_status mrt_denoise_device(const float* d_rgb, const float* d_normal, const float* d_albedo, uint32_t width, uint32_t height,
+                              const mrt_denoise_params* p, float* d_out, float* d_tmp, void* stream);
+        /* whole row-major frames (e.g. after mrt_gather_frame, which moves any float4 shard); d_rgb is not
+           written; d_out, d_tmp: W*H float4 each; enqueued, no sync, no allocation */
+
 /* ---- multi-GPU: the framebuffer gather over RCCL (xGMI) ---------------------------------------
  * The reference's seam is main.cpp:347-382 (the worker threads over one work_queue) writing
  * G_linearBackBuffer (main.cpp:58): here each rank renders the work_queue tiles dealt to it

@@ -173,6 +173,20 @@ class Renderer:
         check(lib().mrt_render_device(self._h, C.byref(desc), C.c_void_p(d_out_ptr), C.c_void_p(d_rays_ptr),
                                       C.c_void_p(stream_ptr)), "mrt_render_device")
 
+    def render_aux(self, desc):
+        """First-hit feature buffers of desc's pixels (include/mrt.h mrt_render_aux), both backends:
+        (normal, albedo), float32 (H, W, 4) each -- normal = (n.xyz facing the ray, coverage), albedo =
+        (r, g, b, depth), the mean over the desc's samples; only owned pixels are written."""
+        normal = np.zeros((desc.height, desc.width, 4), dtype=np.float32)
+        albedo = np.zeros((desc.height, desc.width, 4), dtype=np.float32)
+        check(lib().mrt_render_aux(self._h, C.byref(desc), normal.ctypes.data, albedo.ctypes.data), "mrt_render_aux")
+        return normal, albedo
+
+    def render_aux_device(self, desc, d_normal_ptr, d_albedo_ptr, stream_ptr=0):
+        """Enqueue the feature buffers into device memory (n_local float4 each, local_pixels order)."""
+        check(lib().mrt_render_aux_device(self._h, C.byref(desc), C.c_void_p(d_normal_ptr), C.c_void_p(d_albedo_ptr),
+                                          C.c_void_p(stream_ptr)), "mrt_render_aux_device")
+
     def join(self, stream_ptr=0):
         """Order a HIP stream after this context's last render_device (its fold runs on the context's
         own stream under RF_FOLD_ASYNC): the worker threads' join() (main.cpp:490-493)."""
@@ -293,6 +307,37 @@ def tonemap_device(d_rgb_ptr, n, d_lwmax_ptr, d_argb_ptr, stream_ptr=0, reduce=T
         check(lib().mrt_lum_max_device(C.c_void_p(d_rgb_ptr), n, C.c_void_p(d_lwmax_ptr), C.c_void_p(stream_ptr)), "mrt_lum_max_device")
     check(lib().mrt_tonemap_device(C.c_void_p(d_rgb_ptr), n, C.c_void_p(d_lwmax_ptr), C.c_void_p(d_argb_ptr), C.c_void_p(stream_ptr)),
           "mrt_tonemap_device")
+
+
+def default_denoise_params():
+    """mrt_denoise_params with the library's defaults (iterations, sigma_color, sigma_normal,
+    sigma_albedo, sigma_depth)."""
+    p = _lib.MrtDenoiseParams()
+    lib().mrt_default_denoise_params(C.byref(p))
+    return p
+
+
+def denoise(img, normal, albedo, params=None):
+    """Edge-avoiding a-trous filter (include/mrt_denoise.h) of a host (H, W, 4) float32 image with
+    its feature buffers (Renderer.render_aux); returns the filtered (H, W, 4) image."""
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    normal = np.ascontiguousarray(normal, dtype=np.float32)
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4 or normal.shape != img.shape or albedo.shape != img.shape:
+        raise ValueError("denoise: img, normal and albedo must be (H, W, 4) arrays of one shape")
+    p = params if params is not None else default_denoise_params()
+    h, w = img.shape[:2]
+    out = np.zeros_like(img)
+    check(lib().mrt_denoise(img.ctypes.data, normal.ctypes.data, albedo.ctypes.data, w, h, C.byref(p), out.ctypes.data), "mrt_denoise")
+    return out
+
+
+def denoise_device(d_rgb_ptr, d_normal_ptr, d_albedo_ptr, width, height, d_out_ptr, d_tmp_ptr, params=None, stream_ptr=0):
+    """The same filter on whole row-major device frames (W*H float4 each, torch data_ptr()s), enqueued
+    on a HIP stream: the result lands in d_out; d_tmp is scratch; d_rgb is not written."""
+    p = params if params is not None else default_denoise_params()
+    check(lib().mrt_denoise_device(C.c_void_p(d_rgb_ptr), C.c_void_p(d_normal_ptr), C.c_void_p(d_albedo_ptr), width, height,
+                                   C.byref(p), C.c_void_p(d_out_ptr), C.c_void_p(d_tmp_ptr), C.c_void_p(stream_ptr)), "mrt_denoise_device")
 
 
 def tonemap_argb(img):

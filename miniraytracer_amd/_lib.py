@@ -74,6 +74,12 @@ FT_LIN = 1 << 11  # kernel feature bit: linear hit program (mrt_lin.h)
 FT_VSUB = 1 << 14  # kernel feature bit: volumes bounded by sub-programs (mrt_lin.h lin_sub_t; Cornell smoke)
 
 
+class MrtDenoiseParams(C.Structure):
+    """mrt_denoise_params (include/mrt.h): the a-trous filter's passes and edge-stopping widths."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class MrtError(RuntimeError):
     pass
 
@@ -158,6 +164,17 @@ def lib():
     L.mrt_gather_frame.restype = st
     L.mrt_render_gather.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(MrtRenderDesc), C.c_void_p, C.POINTER(C.c_uint64)]
     L.mrt_render_gather.restype = st
+    L.mrt_render_aux.argtypes = [C.c_void_p, C.POINTER(MrtRenderDesc), C.c_void_p, C.c_void_p]
+    L.mrt_render_aux.restype = st
+    L.mrt_render_aux_device.argtypes = [C.c_void_p, C.POINTER(MrtRenderDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mrt_render_aux_device.restype = st
+    L.mrt_default_denoise_params.argtypes = [C.POINTER(MrtDenoiseParams)]
+    L.mrt_default_denoise_params.restype = None
+    L.mrt_denoise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(MrtDenoiseParams), C.c_void_p]
+    L.mrt_denoise.restype = st
+    L.mrt_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(MrtDenoiseParams),
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mrt_denoise_device.restype = st
     _lib = L
     return L
 
@@ -178,4 +195,5 @@ EXPORTS = [
     "mrt_scene_kernel_info", "mrt_preview", "mrt_lum_max_device", "mrt_tonemap_device", "mrt_worker_seeds", "mrt_set_worker_seeds",
     "mrt_abi_version", "mrt_comm_unique_id", "mrt_comm_init_rank", "mrt_comm_init_all", "mrt_comm_free",
     "mrt_gather_shard_pixels", "mrt_gather_frame", "mrt_render_gather",
+    "mrt_render_aux", "mrt_render_aux_device", "mrt_default_denoise_params", "mrt_denoise", "mrt_denoise_device",
 ]

@@ -14,12 +14,18 @@
 // gather over xGMI plus a device scatter assemble the frame on GPU 0 (mrt_comm_init_all: one
 // communicator per GPU in this process); host: each rank's mrt_render copies its own pixels into the
 // shared host framebuffer (the only choice when ranks share a GPU, or with -backend cpu).
+// -aux PREFIX writes the first-hit feature buffers (mrt_render_aux, at min(spp, 16) samples) as
+// PREFIX_normal.pfm and PREFIX_albedo.pfm; -denoise N filters the image with N a-trous passes over
+// those buffers (mrt_denoise, the library's default widths) before -o writes it.  Both work with
+// every backend and -gpus count: each rank fills its own pixels of the shared host buffers.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/mrt.h"
@@ -34,9 +40,17 @@ int main(int argc, char** argv) {
     if (mrt_parse_argv(argc, argv, &p) != MRT_OK) return 0;  // -help
     const char* out = nullptr;
     const char* gather = nullptr;
+    const char* aux = nullptr;
+    int denoise = -1;
     for (int i = 1; i + 1 < argc; i++) {
         if (!strcmp(argv[i], "-o")) out = argv[i + 1];
         if (!strcmp(argv[i], "-gather")) gather = argv[i + 1];
+        if (!strcmp(argv[i], "-aux")) aux = argv[i + 1];
+        if (!strcmp(argv[i], "-denoise")) denoise = atoi(argv[i + 1]);
+    }
+    if (denoise > 16) {
+        fprintf(stderr, "-denoise: 0 to 16 passes\n");
+        return 1;
     }
     if (gather && strcmp(gather, "rccl") && strcmp(gather, "host")) {
         fprintf(stderr, "-gather: rccl or host\n");
@@ -129,6 +143,43 @@ int main(int argc, char** argv) {
            secs, (total * 0.000001) / secs, (secs * 1000000.0) / (double)total, where, descs[0].sqrt_samples * descs[0].sqrt_samples,
            p.numerics ? "fast" : "exact");
     printf("rays %llu\n", (unsigned long long)total);
+
+    // -aux / -denoise: the first-hit feature buffers at min(spp, 16) samples -- every rank writes its
+    // own pixels of the shared host buffers, as mrt_render does -- then the a-trous filter over the
+    // assembled frame, in place of the image -o writes
+    if (aux || denoise >= 0) {
+        const size_t npx = (size_t)p.buffer_width * p.buffer_height;
+        std::vector<float> nrm(npx * 4, 0.0f), alb(npx * 4, 0.0f);
+        th.clear();
+        for (int r = 0; r < world; r++)
+            th.emplace_back([&, r] {
+                mrt_render_desc ad = descs[r];
+                ad.sqrt_samples = std::min(ad.sqrt_samples, 4u);
+                ad.flags = 0;
+                sts[r] = mrt_render_aux(scenes[r], &ad, nrm.data(), alb.data());
+            });
+        for (auto& t : th) t.join();
+        for (int r = 0; r < world; r++)
+            if (sts[r]) return fail("render_aux", sts[r]);
+        if (aux) {
+            const std::pair<const char*, const std::vector<float>*> files[2] = {{"_normal.pfm", &nrm}, {"_albedo.pfm", &alb}};
+            for (const auto& fl : files) {
+                FILE* f = fopen((std::string(aux) + fl.first).c_str(), "wb");
+                if (!f) return fail("open -aux output", MRT_ERR_IO);
+                fprintf(f, "PF\n%u %u\n-1.0\n", p.buffer_width, p.buffer_height);
+                for (size_t i = 0; i < npx; i++) fwrite(&(*fl.second)[i * 4], 4, 3, f);
+                fclose(f);
+            }
+        }
+        if (denoise >= 0) {
+            mrt_denoise_params dp;
+            mrt_default_denoise_params(&dp);
+            dp.iterations = (uint32_t)denoise;
+            auto t1 = std::chrono::steady_clock::now();
+            if ((st = mrt_denoise(img.data(), nrm.data(), alb.data(), p.buffer_width, p.buffer_height, &dp, img.data()))) return fail("denoise", st);
+            printf("denoise: %d passes, %.1f ms\n", denoise, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+        }
+    }
 
     if (out) {
         std::string o = out;

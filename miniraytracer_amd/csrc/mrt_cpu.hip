@@ -40,6 +40,7 @@
 
 #include "mrt_cpu.h"
 #include "mrt_tables.h"
+#include "mrt_aux.h"
 
 using namespace mrtd;
 
@@ -362,6 +363,58 @@ mrt_status mrt_cpu_render(mrt_cpu_scene* c, const mrt_render_desc* d, float* rgb
     c->last_threads = n;
     if (rays_out) *rays_out = rays.load();
     if (cancelled.load()) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled (partial image)");
+    return MRT_OK;
+}
+
+// First-hit feature buffers (include/mrt.h mrt_render_aux): the loop of mrt_aux_kernel (mrt_aux.hip)
+// over this rank's local pixels -- per pixel its samples in order, each the path's own stream and
+// camera ray and one scene hit (mrt_aux.h) -- on worker threads that take 64 pixels at a time.
+template <uint32_t F>
+static void aux_pixels(const mrt_cpu_scene* c, const mrt_render_desc* d, const std::vector<uint32_t>& px, std::atomic<size_t>& next,
+                       float* normal_out, float* albedo_out) {
+    const DScene& S = c->S;
+    const uint32_t sq = d->sqrt_samples, ns = sq * sq, W = d->width;
+    Stacks st(c->T, 1);
+    const LStack Ls{st.frames.data(), st.rays.data(), st.mesh.data(), st.save.data(), 0u, nullptr, 0u};
+    std::vector<float2> sd(ns);
+    for (uint32_t i = 0; i < sq; i++)
+        for (uint32_t j = 0; j < sq; j++) sd[(size_t)i * sq + j] = make_float2(((float)i + 0.5f) / (float)sq, ((float)j + 0.5f) / (float)sq);
+    for (;;) {
+        const size_t k0 = next.fetch_add(64, std::memory_order_relaxed);
+        if (k0 >= px.size()) break;
+        for (size_t k = k0; k < std::min(k0 + 64, px.size()); k++) {
+            const uint32_t pix = px[k], x = pix % W, y = pix / W;
+            AuxSum a = aux_zero();
+            for (uint32_t s = 0; s < ns; s++) {
+                const uint64_t path_id = (uint64_t)pix * ns + s;
+                PathState ps;
+                pcg_seed(ps.rng, splitmix64(d->seed ^ path_id), path_id);
+                const float u = ((float)x + sd[s].x) / (float)d->width, v = ((float)y + sd[s].y) / (float)d->height;
+                ps.r = camera_ray(S, ps.rng, u, v);
+                aux_first_hit<F>(S, ps, Ls, a);
+            }
+            float4 n4, a4;
+            aux_finish(a, ns, &n4, &a4);
+            memcpy(normal_out + (size_t)pix * 4, &n4, 16);
+            memcpy(albedo_out + (size_t)pix * 4, &a4, 16);
+        }
+    }
+}
+
+mrt_status mrt_cpu_render_aux(mrt_cpu_scene* c, const mrt_render_desc* d, float* normal_out, float* albedo_out) {
+    const std::vector<uint32_t> px = mrt_internal_local_pixels(d);
+    // (desc.threads is not read: one first hit per sample is little work, at most 16 workers share it)
+    uint32_t n = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    n = (uint32_t)std::min<size_t>(n, std::max<size_t>((px.size() + 63) / 64, 1));
+    std::atomic<size_t> next{0};
+    auto work = [&]() {
+        if (c->feats & FT_LIN) aux_pixels<F_LIN>(c, d, px, next, normal_out, albedo_out);
+        else aux_pixels<F_GEN>(c, d, px, next, normal_out, albedo_out);
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t i = 1; i < n; i++) pool.emplace_back(work);
+    work();
+    for (std::thread& t : pool) t.join();
     return MRT_OK;
 }
 

@@ -25,6 +25,7 @@
 
 #include "mrt_internal.h"
 #include "mrt_launch.h"
+#include "mrt_aux.h"
 #include "mrt_tables.h"
 #include "mrt_cpu.h"
 #include "../../include/mrt_tonemap.h"
@@ -413,6 +414,9 @@ struct mrt_scene {
     // never sees its buffers rewritten or freed
     hipEvent_t ev_done = nullptr;
     bool ev_done_pending = false;
+    // the same for the last mrt_render_aux_device (it reads the pixel table and the sample grid)
+    hipEvent_t ev_aux = nullptr;
+    bool ev_aux_pending = false;
     // MRT_RF_FOLD_ASYNC: launches alternate between two radiance buffers (parity lpar), renders
     // between two sets of counter slots (rpar); the fold of parity p runs on fstream and ev_fold[p]
     // marks its end, which the next path kernel writing parity p's radiance buffer waits for (folds
@@ -1198,6 +1202,8 @@ extern "C" void mrt_scene_free(mrt_scene* s) {
     if (s->h_prev) (void)hipHostFree(s->h_prev);
     if (s->h_seq) (void)hipHostFree(s->h_seq);
     if (s->ev_done) (void)hipEventDestroy(s->ev_done);
+    if (s->ev_aux_pending) (void)hipEventSynchronize(s->ev_aux);
+    if (s->ev_aux) (void)hipEventDestroy(s->ev_aux);
     if (s->fstream) (void)hipStreamDestroy(s->fstream);
     for (hipEvent_t e : {s->ev_kern, s->ev_fold[0], s->ev_fold[1]})
         if (e) (void)hipEventDestroy(e);
@@ -1228,6 +1234,10 @@ static mrt_status quiesce(mrt_scene* s) {
     if (s->ev_done_pending) {
         HIPCHK(hipEventSynchronize(s->ev_done));
         s->ev_done_pending = false;
+    }
+    if (s->ev_aux_pending) {
+        HIPCHK(hipEventSynchronize(s->ev_aux));
+        s->ev_aux_pending = false;
     }
     return MRT_OK;
 }
@@ -1363,6 +1373,7 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
     }
     if (!s->pstream) HIPCHK(hipStreamCreateWithFlags(&s->pstream, hipStreamNonBlocking));
     if (!s->ev_done) HIPCHK(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
+    if (!s->ev_aux) HIPCHK(hipEventCreateWithFlags(&s->ev_aux, hipEventDisableTiming));
     {
         std::lock_guard<std::mutex> lk(s->prog_mu);
         if (s->h_prog_cap < (size_t)launches) {
@@ -1618,6 +1629,90 @@ extern "C" mrt_status mrt_render(mrt_scene* s, const mrt_render_desc* d, float* 
     HIPCHK(hipMemcpy(&rays, s->d_rays, 8, hipMemcpyDeviceToHost));
     if (rays_out) *rays_out = rays;
     if (cancelled) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled (partial image)");
+    return MRT_OK;
+}
+
+// ---- first-hit feature buffers (include/mrt.h "feature buffers and denoise") ----
+// what both entry points read of the desc; flags: 0 or MRT_RF_FAST (ignored: the buffers come from
+// the exact arithmetic's hit code on both backends)
+static mrt_status aux_check(const char* who, const mrt_scene* s, const mrt_render_desc* d, const void* normal, const void* albedo) {
+    if (!s || !d || !normal || !albedo) return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": null").c_str());
+    if (d->width == 0 || d->height == 0 || d->sqrt_samples == 0 || (d->world && d->rank >= d->world))
+        return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": bad desc").c_str());
+    if (d->flags & ~MRT_RF_FAST)
+        return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": flags other than MRT_RF_FAST").c_str());
+    return mrt_internal_check_pixels(d);
+}
+
+extern "C" mrt_status mrt_render_aux_device(mrt_scene* s, const mrt_render_desc* d, float* d_normal, float* d_albedo, void* stream) {
+    MRT_GPU_ONLY(s, "mrt_render_aux_device");
+    mrt_status st = aux_check("mrt_render_aux_device", s, d, d_normal, d_albedo);
+    if (st) return st;
+    // the pixel table and the sample grid are the render's (mrt_prepare); nothing else of the
+    // workspace is used, and no flag of the render path applies
+    mrt_render_desc dc = *d;
+    dc.flags = 0;
+    if ((st = mrt_prepare(s, &dc))) return st;
+    if (s->npix == 0) return MRT_OK;
+    const aux_kernel_t fn = aux_kernel_table().kernel[s->variant];
+    const PathLaunch& PL = s->pl[0];  // the exact build's stack sizes
+    PathParams P{};
+    P.sc = s->S;
+    P.lds_frames = s->lds_frames;
+    P.lds_rays = s->lds_rays;
+    P.lds_mesh = PL.lds_mesh;
+    P.lds_save = PL.lds_save;
+    P.pixels = s->d_pixels;
+    P.sdist = s->d_sdist;
+    P.npix = s->npix;
+    P.inv_npix = 1.0 / (double)s->npix;
+    P.width = d->width;
+    P.height = d->height;
+    P.inv_w = 1.0f / (float)d->width;
+    P.inv_h = 1.0f / (float)d->height;
+    P.fast_uv = 1;
+    P.sq = d->sqrt_samples;
+    P.ns = d->sqrt_samples * d->sqrt_samples;
+    P.seed = d->seed;
+    const size_t lds_bytes = (size_t)64 * 4 * (P.lds_frames * 2 + P.lds_rays * 11 + P.lds_mesh + P.lds_save);
+    hipStream_t q = (hipStream_t)stream;
+    hipLaunchKernelGGL(fn, dim3((s->npix + 63u) / 64u), dim3(64), lds_bytes, q, P, (float4*)d_normal, (float4*)d_albedo);
+    HIPCHK(hipGetLastError());
+    // a later change of the pixel table or the sample grid waits for this kernel (quiesce); not
+    // while `stream` is being captured: nothing runs now, and a captured event cannot be waited for
+    // on the host (the caller keeps the layout while it replays the graph)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (q) HIPCHK(hipStreamIsCapturing(q, &cap));
+    if (cap == hipStreamCaptureStatusNone) {
+        HIPCHK(hipEventRecord(s->ev_aux, q));
+        s->ev_aux_pending = true;
+    }
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_render_aux(mrt_scene* s, const mrt_render_desc* d, float* normal_out, float* albedo_out) {
+    mrt_status st = aux_check("mrt_render_aux", s, d, normal_out, albedo_out);
+    if (st) return st;
+    if (s->cpu) return mrt_cpu_render_aux(s->cpu, d, normal_out, albedo_out);
+    mrt_render_desc dc = *d;
+    dc.flags = 0;
+    if ((st = mrt_prepare(s, &dc))) return st;
+    const std::vector<uint32_t> px = mrt_internal_local_pixels(d);
+    if (px.empty()) return MRT_OK;
+    float* dev = nullptr;  // normal, then albedo: n_local float4 each
+    if (hipMalloc((void**)&dev, px.size() * 32) != hipSuccess) return mrt_internal_fail(MRT_ERR_OOM, "mrt_render_aux: device buffers");
+    std::vector<float> local(px.size() * 8);
+    st = mrt_render_aux_device(s, d, dev, dev + px.size() * 4, nullptr);
+    hipError_t e = hipSuccess;
+    if (!st) e = hipMemcpy(local.data(), dev, local.size() * 4, hipMemcpyDeviceToHost);  // (waits for the kernel)
+    (void)hipFree(dev);
+    if (st) return st;
+    if (e != hipSuccess) return mrt_internal_fail(MRT_ERR_HIP, hipGetErrorString(e));
+    s->ev_aux_pending = false;
+    for (size_t i = 0; i < px.size(); i++) {
+        memcpy(normal_out + (size_t)px[i] * 4, &local[i * 4], 16);
+        memcpy(albedo_out + (size_t)px[i] * 4, &local[(px.size() + i) * 4], 16);
+    }
     return MRT_OK;
 }
 
