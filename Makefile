@@ -18,7 +18,7 @@ OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
            $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_denoise.o \
-           $(OBJDIR)/mrt_cpu.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
+           $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
 # (-fno-hip-fp32-correctly-rounded-divide-sqrt: f32 division by v_rcp_f32 + multiply instead of
@@ -60,6 +60,12 @@ $(OBJDIR)/mrt_cpu.o: $(CSRC)/mrt_cpu.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(HOSTFMA) --offload-host-only -c $< -o $@
 
+# the scene compiler (view -> SceneTables, both backends): host code only, and no -mfma -- its float
+# arithmetic (dielectric quotients, box.h recognition) is built as it was inside mrt_render.hip
+$(OBJDIR)/mrt_tables.o: $(CSRC)/mrt_tables.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) --offload-host-only -c $< -o $@
+
 # the first-hit feature buffers (mrt_aux_kernel<F>): the exact contract's hit code in a translation
 # unit of its own, so the path-kernel objects above do not change with it
 $(OBJDIR)/mrt_aux.o: $(CSRC)/mrt_aux.hip $(HDRS)
@@ -90,7 +96,21 @@ bin/mrt: $(CSRC)/mrt_cli.cpp miniraytracer_amd/libmrt.so include/mrt.h
 oracle/liboracle.so: oracle/mrt_oracle.c oracle/mrt_oracle.h include/mrt_scene.h
 	$(CC) -O2 -std=c11 -fPIC -shared -ffp-contract=off -fno-fast-math $(HOSTFMA) -Wall -o $@ oracle/mrt_oracle.c -lm -lpthread
 
+# The scene compiler stand-alone on the CPU under AddressSanitizer + UBSan (host code only, nothing
+# preloaded; not part of `all`): tools/tables_check.cpp builds the tables of scenes 0-9 under every
+# test hook, tools/tables_digest.py --compare checks its digests against tests/golden/tables_parent.json
+TABLES_CHECK_SRC = tools/tables_check.cpp $(CSRC)/mrt_tables.hip $(CSRC)/scene_builder.cpp $(CSRC)/mrt_common.cpp
+SANFLAGS = -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all -g
+build/tables_check: $(TABLES_CHECK_SRC) $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) --offload-host-only -x hip $(SANFLAGS) $(TABLES_CHECK_SRC) -ldl -o $@
+
+tables-check: build/tables_check
+	python3 tools/pack_assets.py --unpack
+	MRT_ASSET_DIR=assets build/tables_check > build/tables_check.out
+	python3 tools/tables_digest.py --compare < build/tables_check.out
+
 clean:
 	rm -rf build miniraytracer_amd/libmrt.so bin oracle/liboracle.so
 
-.PHONY: all clean
+.PHONY: all clean tables-check

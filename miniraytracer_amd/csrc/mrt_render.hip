@@ -13,11 +13,9 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <mutex>
-#include <thread>
 
 #include <algorithm>
-#include <functional>
-#include <cstdio>
+#include <memory>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -38,12 +36,10 @@ using namespace mrtd;
         if (e_ != hipSuccess) return mrt_internal_fail(MRT_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(e_)).c_str()); \
     } while (0)
 
-// The tolerance contract's kernels: the plain fast build, with the kFtzVariant variants taken
-// from the denormal-flushing build (mrt_launch.h); MRT_FTZ=0 in the environment keeps the plain
-// build for every variant (A/B).
-// the tolerance contract's kernels: per variant the path-exact build (kPathExact), else the
+// The tolerance contract's kernels: per variant the path-exact build (kPathExact), else the
 // denormal-flushing build (kFtzVariant), else the plain fast build -- the variant's whole column
-// (a build's workgroup shape, LDS fold levels and walk flags follow its own switches)
+// (a build's workgroup shape, LDS fold levels and walk flags follow its own switches).
+// MRT_PATH_EXACT=0 / MRT_FTZ=0 in the environment skip a build for every variant (A/B).
 static void take_variant(KernelTable& m, const KernelTable& s, uint32_t i) {
     m.kernel[i] = s.kernel[i];
     m.lev_k[i] = s.lev_k[i];
@@ -319,43 +315,30 @@ struct PathLaunch {
     uint32_t wg = 64;     // threads per workgroup
     uint32_t tree_n = 0;  // BvhWide nodes kept in each workgroup's LDS (treelet kernels)
     uint32_t lds_save = 0;  // LDS words per lane slot for the query ray parked during instances
-    uint32_t lds_mesh = 0;  // LDS words per lane of the mesh walk's stack
     bool rewrite = false;   // the kernel runs the tolerance-contract program rewrite (s->prog_fast)
     path_kernel_t retrace = nullptr;  // the exact arithmetic for its rounding-critical paths (mrt_retrace_kernel)
-    size_t retrace_lds = 0;
     bool handover = false;  // the kernel hands its rounding-critical paths to it (fast arithmetic)
     uint32_t walk_min = 32;  // resumable mesh walk threshold of this build (PathParams::walk_min)
 };
 
-// Wide nodes renumbered breadth-first over all roots together (level 0 of every tree, then level
-// 1, ...), so the first K nodes of the array are the top levels of the scene's BVHs -- what a
-// treelet of K nodes holds.  Only the labels change: every walk visits the same nodes.
-// limit: only the first `limit` nodes breadth-first, the others after them in their own order
-// (pod_bvh's depth-first layout keeps a subtree's nodes together in the cache).
-template <typename W>
-static void bfs_order(std::vector<W>& wide, std::vector<uint32_t*> roots, uint32_t leaf_bit, uint32_t limit = 0xFFFFFFFFu) {
-    const uint32_t n = (uint32_t)wide.size();
-    std::vector<uint32_t> nid(n, MRT_NONE), order;
-    order.reserve(n);
-    for (uint32_t* r : roots)
-        if (!(*r & leaf_bit) && *r < n && nid[*r] == MRT_NONE && order.size() < limit) { nid[*r] = (uint32_t)order.size(); order.push_back(*r); }
-    for (size_t q = 0; q < order.size() && order.size() < limit; q++) {
-        const W& w = wide[order[q]];
-        for (uint32_t c : {w.lref, w.rref})
-            if (!(c & leaf_bit) && c < n && nid[c] == MRT_NONE && order.size() < limit) { nid[c] = (uint32_t)order.size(); order.push_back(c); }
+// A workspace buffer on the device, grown on demand (mrt_prepare) and freed with its scene.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // the bytes asked for
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    // at least `bytes` (a zero-byte request gets 16); before it reallocates, waits for the scene's
+    // last enqueued render (quiesce)
+    mrt_status grow(mrt_scene* s, size_t bytes);
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
     }
-    for (uint32_t i = 0; i < n; i++)  // the rest (and unreachable nodes) in their own order
-        if (nid[i] == MRT_NONE) { nid[i] = (uint32_t)order.size(); order.push_back(i); }
-    auto remap = [&](uint32_t c) { return (c & leaf_bit) || c >= n ? c : nid[c]; };
-    std::vector<W> out(n);
-    for (uint32_t k = 0; k < n; k++) {
-        out[k] = wide[order[k]];
-        out[k].lref = remap(out[k].lref);
-        out[k].rref = remap(out[k].rref);
-    }
-    wide.swap(out);
-    for (uint32_t* r : roots) *r = remap(*r);
-}
+};
 
 struct mrt_scene {
     int device = 0;
@@ -370,19 +353,18 @@ struct mrt_scene {
     const LinOp* prog_fast = nullptr;  // the tolerance contract's program for the interpreter (lin_rewrite_fast)
     bool have_ws = false;
     uint32_t npix = 0, chunk = 0;
-    uint2* d_pixels = nullptr;
-    float2* d_sdist = nullptr;
+    DevBuf<uint2> d_pixels;
+    DevBuf<float2> d_sdist;
     uint32_t sdist_sq = 0;
-    float* d_rad = nullptr;
-    uint32_t* d_path_rays = nullptr;
-    float4* d_acc = nullptr;
-    float4* d_lev = nullptr;
-    float4* d_out = nullptr;         // mrt_render's device framebuffer (local-pixel order)
+    DevBuf<float> d_rad;
+    DevBuf<uint32_t> d_path_rays;
+    DevBuf<float4> d_acc;
+    DevBuf<float4> d_lev;
+    DevBuf<float4> d_out;            // mrt_render's device framebuffer (local-pixel order)
     // progressive preview (MRT_RF_PREVIEW): device staging image, pinned host copy guarded by a
     // sequence word the render's stream writes around each copy (odd = copy in flight) and the
     // sample count the copy holds
-    float4* d_prev = nullptr;
-    size_t prev_cap = 0;
+    DevBuf<float4> d_prev;
     float4* h_prev = nullptr;
     size_t h_prev_cap = 0;
     uint32_t* h_seq = nullptr;       // [0] sequence, [1] samples folded into h_prev
@@ -393,10 +375,8 @@ struct mrt_scene {
     uint64_t* d_counter = nullptr;   // 64 B scratch: [0] paths handed to the exact arithmetic since upload, [2] ray total of mrt_render, [4] cancel flag,
                                      // [1] rounding-critical paths listed (u32), [3] retrace groups done (u32), [5] listed beyond the cap since upload,
                                      // [6] the parity-1 list's count (u32) and retrace groups done (u32)
-    uint32_t* d_rt = nullptr;        // rounding-critical paths listed for the retrace kernel (path indices)
-    size_t rt_cap = 0;
-    uint64_t* d_counters = nullptr;  // one work counter per chunk launch (progress reads them)
-    size_t cnt_cap = 0;
+    DevBuf<uint32_t> d_rt;           // rounding-critical paths listed for the retrace kernel (path indices)
+    DevBuf<uint64_t> d_counters;     // one work counter per chunk launch (progress reads them)
     std::vector<uint64_t> chunk_paths;
     hipStream_t pstream = nullptr;   // non-blocking stream for the cancel-flag copy
     // host-coherent pinned memory: per-launch snapshots of the work counters, stored by the path
@@ -426,8 +406,7 @@ struct mrt_scene {
     hipEvent_t ev_fold[2] = {nullptr, nullptr};
     bool fold_pending[2] = {false, false};
     uint32_t lpar = 0, rpar = 0;
-    float* d_rad2 = nullptr;
-    size_t rad2_cap = 0;
+    DevBuf<float> d_rad2;
     uint32_t n_cu = 0;
     uint32_t prog_base = 0;  // launch slot of the current render's counters and progress snapshots
     uint32_t slot_half = 0;  // launch slots per set (renders use set rpar at rpar * slot_half; mrt_prepare)
@@ -439,11 +418,17 @@ struct mrt_scene {
     size_t max_threads = 0;  // largest path-kernel grid in threads (per-lane level rows)
     std::vector<hipEvent_t> ev;  // [2*k]: start/stop of path-kernel launch k of the last render
     uint32_t n_launch = 0;
-    size_t rad_cap = 0, acc_cap = 0, lev_cap = 0, px_cap = 0, pr_cap = 0, sd_cap = 0, out_cap = 0;
     uint64_t last_paths = 0;
     uint32_t last_numerics = 0;
     uint32_t prog_ops = 0;  // linear hit program length (0: generic machine)
 };
+
+// LDS words per lane of a launch's walk stacks: the generic machine's frames (two words each) and
+// transformed rays (eleven each), the mesh / bvh_node walk's stack, `lds_save` words for the query ray
+// parked during instances.  The path, retrace and aux launches all size their LDS from it.
+static uint32_t lds_stack_words(const mrt_scene* s, uint32_t lds_save) {
+    return s->lds_frames * 2 + s->lds_rays * 11 + s->lds_mesh + lds_save;
+}
 
 static mrt_status dev_alloc(mrt_scene* s, void** p, size_t bytes) {
     if (bytes == 0) bytes = 16;
@@ -479,560 +464,6 @@ extern "C" mrt_status mrt_init(int* device_count) {
     return MRT_OK;
 }
 
-// graph checks on the host: every device stack is sized from them, so none can overflow
-static bool needs_uv_tex(const mrt_scene_view* v, uint32_t t, int guard = 0) {
-    if (t == MRT_NONE || t >= v->n_textures || guard > 16) return false;
-    const mrt_texture& T = v->textures[t];
-    if (T.kind == MRT_T_IMAGE) return true;
-    if (T.kind == MRT_T_CHECKER) return needs_uv_tex(v, T.a, guard + 1) || needs_uv_tex(v, T.b, guard + 1);
-    return false;
-}
-struct GraphCheck {
-    const std::vector<mrt_node>& nodes;
-    const mrt_scene_view* v;
-    int max_frames = 0, max_rays = 0, max_mesh = 0;
-    int bvhw_depth = 0;  // deepest wide-node stack of the converted bvh_node subtrees
-    bool ok = true;
-    std::string why;
-    int mesh_depth(uint32_t ni, int guard) {
-        if (guard > 1000 || ni >= v->n_mesh_nodes) return 100000;
-        const mrt_mesh_node& m = v->mesh_nodes[ni];
-        if (m.count_order & 0xFFFFFFu) return 1;
-        return 1 + std::max(mesh_depth(m.left_or_first, guard + 1), mesh_depth(m.left_or_first + 1, guard + 1));
-    }
-    void walk(uint32_t id, int frames, int rays, bool in_volume, int guard) {
-        if (!ok) return;
-        if (id >= nodes.size() || guard > 4096) { ok = false; why = "bad node index / cyclic scene graph"; return; }
-        const mrt_node& n = nodes[id];
-        uint32_t k = n.kind & 0xFF;
-        if (k == MRT_K_SPHERE || k == MRT_K_XY || k == MRT_K_XZ || k == MRT_K_YZ) return;
-        if (k == MRT_K_MESH) {
-            max_mesh = std::max(max_mesh, mesh_depth(n.a, 0));
-            return;
-        }
-        if (k == MRT_K_BVHW) {
-            max_mesh = std::max(max_mesh, bvhw_depth);
-            return;
-        }
-        frames++;
-        max_frames = std::max(max_frames, frames);
-        switch (k) {
-        case MRT_K_LIST:
-            for (uint32_t i = 0; i < n.b; i++) walk(v->children[n.a + i], frames, rays, in_volume, guard + 1);
-            break;
-        case MRT_K_BVH:
-            walk(n.a, frames, rays, in_volume, guard + 1);
-            walk(n.b, frames, rays, in_volume, guard + 1);
-            break;
-        case MRT_K_TRANSLATE: case MRT_K_ROTY: case MRT_K_TRROTY:
-            max_rays = std::max(max_rays, rays + 1);
-            walk(n.a, frames, rays + 1, in_volume, guard + 1);
-            break;
-        case MRT_K_VOLUME:
-            if (in_volume) { ok = false; why = "nested constant_volume"; return; }
-            walk(n.a, frames, rays, true, guard + 1);
-            break;
-        default: ok = false; why = "unknown node kind";
-        }
-    }
-};
-
-// Linear hit program (mrt_lin.h): object_list trees of primitives / meshes with at most one
-// instance level.  Returns false (generic kernel) for bvh_node, constant_volume, nested instances.
-struct LinCompiler {
-    const std::vector<mrt_node>& nodes;
-    const mrt_scene_view* v;
-    std::vector<LinOp> prog;
-    int max_lvl = 0;
-    uint32_t inst_pc = MRT_NONE;  // op index of the enclosing instance while its subtree is emitted
-    bool in_vsub = false;         // emitting a volume's boundary sub-program (primitives, lists, one instance level)
-    bool vsub = false;            // the program has such a volume (FT_VSUB)
-    // code = op | kind << 8 | flags << 16 | nesting level << 24 (the level the op is tested at)
-    LinOp op_of(uint32_t code, uint32_t id, int lvl) {
-        const mrt_node& n = nodes[id];
-        LinOp o{};
-        o.code = code | ((n.kind & 0xFFu) << 8) | (n.kind & 0xFF0000u) | ((uint32_t)lvl << 24);
-        o.node = id;
-        o.skip = 0;
-        o.mat = n.mat;
-        for (int i = 0; i < 12; i++) o.f[i] = n.f[i];
-        return o;
-    }
-    // primitive-like ops (prim, mesh, bvh subtree, volume) also carry the enclosing instance's op
-    // index in f[11] (which they do not use) for the resumable interpreter
-    LinOp leaf_op(uint32_t code, uint32_t id, int lvl) {
-        LinOp o = op_of(code, id, lvl);
-        memcpy(&o.f[11], &inst_pc, 4);
-        return o;
-    }
-    bool emit(uint32_t id, int inst_depth, int lvl, int guard) {
-        if (id >= nodes.size() || guard > 256 || lvl > 30) return false;
-        const mrt_node& n = nodes[id];
-        const uint32_t k = n.kind & 0xFFu;
-        max_lvl = std::max(max_lvl, lvl);
-        switch (k) {
-        case MRT_K_SPHERE: case MRT_K_XY: case MRT_K_XZ: case MRT_K_YZ:
-            prog.push_back(leaf_op(LOP_PRIM, id, lvl));
-            return true;
-        case MRT_K_MESH:
-            if (in_vsub) return false;
-            prog.push_back(leaf_op(LOP_MESH, id, lvl));
-            return true;
-        case MRT_K_BVHW: {
-            if (in_vsub) return false;
-            LinOp o = leaf_op(LOP_BVHW, id, lvl);
-            o.skip = n.a;  // the subtree's root ref (the op's f[0..5] are its box)
-            prog.push_back(o);
-            return true;
-        }
-        case MRT_K_VOLUME: {
-            if (n.a >= nodes.size() || in_vsub) return false;
-            const uint32_t bk = nodes[n.a].kind & 0xFFu;
-            if (bk == MRT_K_SPHERE || bk == MRT_K_XY || bk == MRT_K_XZ || bk == MRT_K_YZ) {  // a primitive boundary
-                prog.push_back(leaf_op(LOP_VOLUME, id, lvl));
-                prog.push_back(op_of(LOP_VBOUND, n.a, lvl));
-                return true;
-            }
-            // any other boundary (box.h lists, instances of them: cornell_smoke, scene.cpp:364-369)
-            // as a sub-program after the op, walked twice per query by the volume op (lin_sub_t) and
-            // skipped by the main walk; outside instances only (its instance is then the only level)
-            if (inst_depth > 0) return false;
-            const size_t at = prog.size();
-            LinOp vo = leaf_op(LOP_VOLUME, id, lvl);
-            vo.code |= MRT_F_VSUB << 16;
-            prog.push_back(vo);
-            in_vsub = true;
-            const bool ok = emit(n.a, inst_depth, 0, guard + 1);  // (levels of the sub-program from 0)
-            in_vsub = false;
-            if (!ok) return false;
-            prog[at].skip = (uint32_t)prog.size();
-            vsub = true;
-            return true;
-        }
-        case MRT_K_LIST: {
-            size_t at = prog.size();
-            prog.push_back(op_of(LOP_LIST, id, lvl));
-            for (uint32_t i = 0; i < n.b; i++)
-                if (!emit(v->children[n.a + i], inst_depth, lvl + 1, guard + 1)) return false;
-            prog[at].skip = (uint32_t)prog.size();
-            prog.push_back(op_of(LOP_LIST_END, id, lvl));
-            return true;
-        }
-        case MRT_K_TRANSLATE: case MRT_K_ROTY: case MRT_K_TRROTY: {
-            if (inst_depth > 0) return false;
-            size_t at = prog.size();
-            prog.push_back(op_of(LOP_INST, id, lvl));
-            const uint32_t outer_pc = inst_pc;
-            if (!in_vsub) inst_pc = (uint32_t)at;
-            const bool ok = emit(n.a, inst_depth + 1, lvl + 1, guard + 1);
-            inst_pc = outer_pc;
-            if (!ok) return false;
-            prog[at].skip = (uint32_t)prog.size();
-            LinOp e = op_of(LOP_INST_END, id, lvl);
-            e.skip = (uint32_t)at;  // its instance op
-            prog.push_back(e);
-            return true;
-        }
-        default:
-            return false;
-        }
-    }
-};
-
-static uint32_t scene_features(const mrt_scene_view* v, const std::vector<mrt_node>& nodes, const std::vector<uint8_t>& absorbed) {
-    uint32_t f = 0;
-    for (size_t i = 0; i < nodes.size(); i++) {
-        const mrt_node& n = nodes[i];
-        switch (n.kind & 0xFF) {
-        case MRT_K_BVH: if (!absorbed[i]) f |= FT_BVH; break;
-        case MRT_K_BVHW: f |= FT_BVHW; break;
-        case MRT_K_MESH: f |= FT_MESH; break;
-        case MRT_K_VOLUME: f |= FT_VOLUME; break;
-        case MRT_K_TRANSLATE: case MRT_K_ROTY: case MRT_K_TRROTY: f |= FT_INST; break;
-        case MRT_K_SPHERE: if ((n.kind >> 16) & MRT_F_MOVING) f |= FT_MOVING; break;
-        }
-        if ((n.kind >> 16) & MRT_F_NEEDUV) f |= FT_UV;
-    }
-    for (uint32_t i = 0; i < v->n_textures; i++)
-        if (v->textures[i].kind != MRT_T_COLOR) f |= FT_TEX;
-    for (uint32_t i = 0; i < v->n_materials; i++) {
-        if (v->materials[i].kind == MRT_M_METAL) f |= FT_METAL;
-        if (v->materials[i].kind == MRT_M_ISOTROPIC) f |= FT_ISO;
-    }
-    if (v->sky) f |= FT_SKY;
-    if (v->biased != MRT_NONE) {
-        f |= FT_BIASED;
-        const mrt_node& b = nodes[v->biased];
-        // any leaf but an xz_rect: spheres, and kinds without a pdf of their own (mrt_shade.h predraw_ok)
-        if ((b.kind & 0xFF) != MRT_K_XZ && (b.kind & 0xFF) != MRT_K_LIST) f |= FT_BSPHERE;
-        if ((b.kind & 0xFF) == MRT_K_LIST)
-            for (uint32_t i = 0; i < b.b; i++)
-                if ((nodes[v->children[b.a + i]].kind & 0xFF) != MRT_K_XZ) f |= FT_BSPHERE;
-    }
-    return f;
-}
-
-// Every index a view's records hold, against the array it points into: the table builder below and
-// both backends' walks dereference them unchecked.  Returns what is out of range ("" if nothing is);
-// runs before anything else reads the arrays and before any HIP call.
-static std::string view_range_error(const mrt_scene_view* v) {
-    auto at = [](const char* what, uint32_t i) { return std::string(what) + " (record " + std::to_string(i) + ")"; };
-    if ((v->n_nodes && !v->nodes) || (v->n_children && !v->children) || (v->n_mesh_nodes && !v->mesh_nodes) ||
-        (v->n_tris && (!v->tri_geo || !v->tri_nrm)) || (v->n_materials && !v->materials) || (v->n_textures && !v->textures) ||
-        (v->n_texels && !v->texels) || !v->perlin_ranvec || !v->perlin_perm)
-        return "null array with a non-zero count";
-    if (v->biased != MRT_NONE && v->biased >= v->n_nodes) return "bad biased node";
-    for (uint32_t i = 0; i < v->n_nodes; i++) {
-        const mrt_node& n = v->nodes[i];
-        switch (n.kind & 0xFF) {
-        case MRT_K_LIST:
-            if ((uint64_t)n.a + n.b > v->n_children) return at("object_list children run beyond n_children", i);
-            for (uint32_t c = 0; c < n.b; c++)
-                if (v->children[n.a + c] >= v->n_nodes) return at("object_list child index beyond n_nodes", i);
-            break;
-        case MRT_K_BVH:
-            if (n.a >= v->n_nodes || n.b >= v->n_nodes) return at("bvh_node child index beyond n_nodes", i);
-            break;
-        case MRT_K_MESH:
-            if (n.a >= v->n_mesh_nodes) return at("mesh root beyond n_mesh_nodes", i);
-            if (n.mat >= v->n_materials) return at("mesh material index beyond n_materials", i);
-            break;
-        case MRT_K_TRANSLATE: case MRT_K_ROTY:
-            if (n.a >= v->n_nodes) return at("instance child index beyond n_nodes", i);
-            break;
-        case MRT_K_SPHERE: case MRT_K_XY: case MRT_K_XZ: case MRT_K_YZ:
-            if (n.mat >= v->n_materials) return at("primitive material index beyond n_materials", i);
-            break;
-        case MRT_K_VOLUME:
-            if (n.a >= v->n_nodes) return at("constant_volume boundary index beyond n_nodes", i);
-            if (n.mat >= v->n_materials) return at("constant_volume material index beyond n_materials", i);
-            break;
-        default: break;  // (an unknown kind is refused where the graph reaches it: GraphCheck)
-        }
-    }
-    for (uint32_t i = 0; i < v->n_mesh_nodes; i++) {
-        const mrt_mesh_node& m = v->mesh_nodes[i];
-        const uint32_t cnt = m.count_order & 0xFFFFFFu;
-        if (cnt == 0 ? (uint64_t)m.left_or_first + 1 >= v->n_mesh_nodes : (uint64_t)m.left_or_first + cnt > v->n_tris)
-            return at(cnt == 0 ? "mesh node children beyond n_mesh_nodes" : "mesh leaf triangles beyond n_tris", i);
-    }
-    for (uint32_t i = 0; i < v->n_materials; i++) {
-        const mrt_material& m = v->materials[i];
-        // (a dielectric has no texture: material.h:121)
-        if (m.kind != MRT_M_DIELECTRIC && m.tex >= v->n_textures) return at("material texture index beyond n_textures", i);
-    }
-    for (uint32_t i = 0; i < v->n_textures; i++) {
-        const mrt_texture& t = v->textures[i];
-        if (t.kind == MRT_T_CHECKER && (t.a >= v->n_textures || t.b >= v->n_textures))
-            return at("checker texture child index beyond n_textures", i);
-        if (t.kind == MRT_T_IMAGE && (t.b == 0 || t.c == 0 || (uint64_t)t.b * t.c > (1ull << 40) ||
-                                      (uint64_t)t.a + (uint64_t)t.b * t.c * 3u > v->n_texels))
-            return at("image texture texels beyond n_texels", i);
-    }
-    return "";
-}
-
-// The scene's device tables (mrt_tables.h), built on the host from the caller's view; both
-// backends run on them: mrt_scene_upload copies them to HBM, mrt_cpu_scene_create keeps them.
-mrt_status mrt_internal_scene_tables(const mrt_scene_view* v, SceneTables* T) {
-    if (!v || !T || v->root >= v->n_nodes) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_scene_upload: bad view");
-    {
-        const std::string bad = view_range_error(v);
-        if (!bad.empty()) return mrt_internal_fail(MRT_ERR_INVALID, ("mrt_scene_upload: " + bad).c_str());
-    }
-    // device node table: NEEDUV flags; translate(rotate_y(x)) fused into one instance node
-    std::vector<mrt_node> nodes(v->nodes, v->nodes + v->n_nodes);
-    for (mrt_node& n : nodes) {
-        uint32_t k = n.kind & 0xFF;
-        if ((k == MRT_K_SPHERE || k == MRT_K_XY || k == MRT_K_XZ || k == MRT_K_YZ) && n.mat < v->n_materials &&
-            needs_uv_tex(v, v->materials[n.mat].tex))
-            n.kind |= MRT_F_NEEDUV << 16;
-    }
-    // rect planes outside {0} U [2^-77, 2^60] keep the IEEE division in rect tests (mrt_device.h ray_nice)
-    for (mrt_node& n : nodes) {
-        const uint32_t k = n.kind & 0xFF;
-        if (k != MRT_K_XY && k != MRT_K_XZ && k != MRT_K_YZ) continue;
-        const float c = std::fabs(n.f[4]);
-        if (!(c == 0.0f || (c >= 0x1p-77f && c <= 0x1p60f))) n.kind |= MRT_F_SLOWDIV << 16;
-    }
-    // box.h:12-20 recognised: an object_list of exactly six outward-facing rects over one box
-    // (xy at max z / min z, xz at max y / min y, yz at max x / min x, bounds spanning the box, one
-    // material, no uv, no slow divisions).  Flag MRT_F_BOX6, planes in f[6..11] (min xyz, max xyz):
-    // the tolerance contract tests such a list as one slab test (mrt_sig.h box6_hit).
-    for (size_t i = 0; i < nodes.size(); i++) {
-        mrt_node& n = nodes[i];
-        if ((n.kind & 0xFF) != MRT_K_LIST || n.b != 6 || n.a + 6 > v->n_children) continue;
-        const mrt_node* c[6];
-        bool ok = true;
-        for (int j = 0; j < 6 && ok; j++) {
-            const uint32_t ci = v->children[n.a + j];
-            ok = ci < nodes.size();
-            if (ok) c[j] = &nodes[ci];
-        }
-        if (!ok) continue;
-        static const uint32_t kinds[6] = {MRT_K_XY, MRT_K_XY, MRT_K_XZ, MRT_K_XZ, MRT_K_YZ, MRT_K_YZ};
-        for (int j = 0; j < 6 && ok; j++)
-            ok = (c[j]->kind & 0xFF) == kinds[j] && c[j]->f[5] == ((j & 1) ? -1.0f : 1.0f) && c[j]->mat == c[0]->mat &&
-                 !((c[j]->kind >> 16) & (MRT_F_NEEDUV | MRT_F_SLOWDIV));
-        if (!ok) continue;
-        const float xmin = c[5]->f[4], xmax = c[4]->f[4], ymin = c[3]->f[4], ymax = c[2]->f[4], zmin = c[1]->f[4], zmax = c[0]->f[4];
-        auto span = [&](const mrt_node* r, float a0, float a1, float b0, float b1) {
-            return r->f[0] == a0 && r->f[1] == a1 && r->f[2] == b0 && r->f[3] == b1;
-        };
-        ok = xmin < xmax && ymin < ymax && zmin < zmax && span(c[0], xmin, xmax, ymin, ymax) && span(c[1], xmin, xmax, ymin, ymax) &&
-             span(c[2], xmin, xmax, zmin, zmax) && span(c[3], xmin, xmax, zmin, zmax) && span(c[4], ymin, ymax, zmin, zmax) &&
-             span(c[5], ymin, ymax, zmin, zmax);
-        if (!ok) continue;
-        n.kind |= MRT_F_BOX6 << 16;
-        n.mat = c[0]->mat;  // (an object_list has no material of its own)
-        n.f[6] = xmin; n.f[7] = ymin; n.f[8] = zmin;
-        n.f[9] = xmax; n.f[10] = ymax; n.f[11] = zmax;
-    }
-    for (mrt_node& n : nodes) {
-        if ((n.kind & 0xFF) != MRT_K_TRANSLATE || n.a >= nodes.size()) continue;
-        const mrt_node& c = nodes[n.a];
-        if ((c.kind & 0xFF) != MRT_K_ROTY) continue;
-        mrt_node f{};
-        f.kind = MRT_K_TRROTY | (c.kind & (MRT_F_HASBOX << 16));
-        f.a = c.a;
-        f.b = MRT_NONE;
-        f.mat = MRT_NONE;
-        for (int i = 0; i < 8; i++) f.f[i] = c.f[i];  // bbox, sin, cos
-        f.f[8] = n.f[0]; f.f[9] = n.f[1]; f.f[10] = n.f[2];
-        n = f;
-    }
-    // pod_bvh -> wide nodes (both child boxes inline); MESH nodes get b = root ref
-    std::vector<MeshWide> wide;
-    {
-        std::vector<uint32_t> wide_of(v->n_mesh_nodes, MRT_NONE);
-        for (uint32_t i = 0; i < v->n_mesh_nodes; i++)
-            if ((v->mesh_nodes[i].count_order & 0xFFFFFFu) == 0) {
-                wide_of[i] = (uint32_t)wide.size();
-                wide.push_back(MeshWide{});
-            }
-        bool ok = wide.size() < MESH_LEAF;
-        auto ref_of = [&](uint32_t i) -> uint32_t {
-            if (i >= v->n_mesh_nodes) { ok = false; return 0; }
-            const mrt_mesh_node& m = v->mesh_nodes[i];
-            const uint32_t cnt = m.count_order & 0xFFFFFFu;
-            if (cnt == 0) return wide_of[i];
-            if (cnt > 0x7Fu || m.left_or_first > 0xFFFFFFu) ok = false;
-            if ((MESH_LEAF | (cnt << 24) | m.left_or_first) >= kMeshEmpty) ok = false;  // (the walk's marks)
-            return MESH_LEAF | (cnt << 24) | m.left_or_first;
-        };
-        for (uint32_t i = 0; i < v->n_mesh_nodes && ok; i++) {
-            if (wide_of[i] == MRT_NONE) continue;
-            const mrt_mesh_node& m = v->mesh_nodes[i];
-            const uint32_t l = m.left_or_first;
-            if (l + 1 >= v->n_mesh_nodes) { ok = false; break; }
-            MeshWide& W = wide[wide_of[i]];
-            const mrt_mesh_node &L = v->mesh_nodes[l], &R = v->mesh_nodes[l + 1];
-            for (int k = 0; k < 3; k++) {
-                W.lmin[k] = L.bmin[k]; W.lmax[k] = L.bmax[k];
-                W.rmin[k] = R.bmin[k]; W.rmax[k] = R.bmax[k];
-            }
-            W.lref = ref_of(l);
-            W.rref = ref_of(l + 1);
-            W.order = m.count_order >> 24;
-        }
-        for (mrt_node& n : nodes)
-            if ((n.kind & 0xFF) == MRT_K_MESH) n.b = ref_of(n.a);
-        if (!ok) return mrt_internal_fail(MRT_ERR_INVALID, "mesh BVH outside the device encoding (leaf > 127 triangles or > 2^24 triangles)");
-        // the top 63 nodes first, breadth-first: the hot top levels share cache lines
-        std::vector<uint32_t*> mroots;
-        for (mrt_node& n : nodes)
-            if ((n.kind & 0xFF) == MRT_K_MESH) mroots.push_back(&n.b);
-        bfs_order(wide, mroots, MESH_LEAF, 63u);
-    }
-    // bvh_node subtrees whose leaves are primitives / object_lists of primitives (and of boxes of
-    // primitives) -> wide nodes; the subtree root becomes an MRT_K_BVHW node (a = root ref)
-    std::vector<BvhWide> bwide;
-    std::vector<mrt_node> bprims;  // leaf primitive runs of the wide subtrees
-    int bvhw_depth = 0;
-    std::vector<uint8_t> absorbed(nodes.size(), 0);  // bvh_nodes now inside a wide subtree
-    {
-        const size_t nn = nodes.size();
-        auto kind_of = [&](uint32_t i) { return nodes[i].kind & 0xFFu; };
-        auto is_leaf_prim = [&](uint32_t i) {
-            const uint32_t k = kind_of(i);
-            return k == MRT_K_SPHERE || k == MRT_K_XY || k == MRT_K_XZ || k == MRT_K_YZ;
-        };
-        auto leaf_ok = [&](uint32_t i) {
-            if (is_leaf_prim(i)) return true;
-            if (kind_of(i) != MRT_K_LIST) return false;
-            const mrt_node& l = nodes[i];
-            for (uint32_t c = 0; c < l.b; c++) {
-                const uint32_t ci = v->children[l.a + c];
-                if (ci >= nn) return false;
-                if (is_leaf_prim(ci)) continue;
-                if (kind_of(ci) != MRT_K_LIST) return false;
-                const mrt_node& g = nodes[ci];
-                for (uint32_t j = 0; j < g.b; j++) {
-                    const uint32_t gi = v->children[g.a + j];
-                    if (gi >= nn || !is_leaf_prim(gi)) return false;
-                }
-            }
-            return true;
-        };
-        std::vector<uint8_t> under_bvh(nn, 0);
-        for (size_t i = 0; i < nn; i++)
-            if (kind_of((uint32_t)i) == MRT_K_BVH) {
-                if (nodes[i].a < nn) under_bvh[nodes[i].a] = 1;
-                if (nodes[i].b < nn) under_bvh[nodes[i].b] = 1;
-            }
-        // does the subtree at i qualify (bvh_node inner nodes, qualifying leaves)?
-        std::function<bool(uint32_t, int)> ok = [&](uint32_t i, int guard) -> bool {
-            if (i >= nn || guard > 64) return false;
-            if (kind_of(i) != MRT_K_BVH) return leaf_ok(i);
-            return ok(nodes[i].a, guard + 1) && ok(nodes[i].b, guard + 1);
-        };
-        // a leaf's primitives as one contiguous run of node records (bprims): a primitive leaf is a
-        // run of one; an object_list leaf is its children in order, a nested object_list as a LIST
-        // record (its box, b = the count of its own children that follow) before its children.  The
-        // walk then fetches a leaf's records at independent addresses instead of through the
-        // children[] -> node chain (two dependent loads per primitive).
-        bool leaves_ok = true;
-        auto emit_leaf = [&](uint32_t i) -> uint32_t {
-            const uint32_t first = (uint32_t)bprims.size();
-            if (is_leaf_prim(i)) {
-                bprims.push_back(nodes[i]);
-            } else {
-                const mrt_node& l = nodes[i];
-                for (uint32_t c = 0; c < l.b; c++) {
-                    const uint32_t ci = v->children[l.a + c];
-                    if (is_leaf_prim(ci)) { bprims.push_back(nodes[ci]); continue; }
-                    const mrt_node& g = nodes[ci];
-                    mrt_node m = g;
-                    m.b = g.b;
-                    bprims.push_back(m);
-                    for (uint32_t j = 0; j < g.b; j++) bprims.push_back(nodes[v->children[g.a + j]]);
-                }
-            }
-            const uint32_t cnt = (uint32_t)bprims.size() - first;
-            if (cnt > BVHW_MAX_RUN || first > BVHW_FIRST_MASK) leaves_ok = false;
-            if ((BVHW_LEAF | (cnt << 24) | (first & BVHW_FIRST_MASK)) == kBvhwEmpty) leaves_ok = false;  // (the walk's empty-stack mark)
-            return BVHW_LEAF | (cnt << 24) | (first & BVHW_FIRST_MASK);
-        };
-        std::function<uint32_t(uint32_t, int)> build = [&](uint32_t i, int depth) -> uint32_t {
-            bvhw_depth = std::max(bvhw_depth, depth);
-            if (kind_of(i) != MRT_K_BVH) return emit_leaf(i);
-            absorbed[i] = 1;
-            const uint32_t w = (uint32_t)bwide.size();
-            bwide.push_back(BvhWide{});
-            const mrt_node& b = nodes[i];
-            const uint32_t lc = b.a, rc = b.b;
-            const uint32_t lref = build(lc, depth + 1), rref = build(rc, depth + 1);
-            BvhWide& W = bwide[w];
-            W.lref = lref;
-            W.rref = rref;
-            W.order = (b.kind >> 8) & 0xFFu;
-            W.flags = 0;
-            const mrt_node &L = nodes[lc], &R = nodes[rc];
-            auto has_box = [&](const mrt_node& c) {
-                const uint32_t k = c.kind & 0xFFu;
-                return k == MRT_K_BVH || (k == MRT_K_LIST && ((c.kind >> 16) & MRT_F_HASBOX));
-            };
-            if (has_box(L)) { W.flags |= 1u; for (int k = 0; k < 3; k++) { W.lmin[k] = L.f[k]; W.lmax[k] = L.f[3 + k]; } }
-            if (has_box(R)) { W.flags |= 2u; for (int k = 0; k < 3; k++) { W.rmin[k] = R.f[k]; W.rmax[k] = R.f[3 + k]; } }
-            return w;
-        };
-        const char* no_bvhw = getenv("MRT_NO_BVHW");  // test hook: keep the generic bvh_node walk
-        if (!(no_bvhw && *no_bvhw && *no_bvhw != '0'))
-            for (size_t i = 0; i < nn; i++)
-                if (kind_of((uint32_t)i) == MRT_K_BVH && !under_bvh[i] && ok((uint32_t)i, 0) && bwide.size() < BVHW_LEAF / 2) {
-                    const uint32_t root = build((uint32_t)i, 1);
-                    mrt_node& r = nodes[i];
-                    r.kind = (r.kind & ~0xFFu) | MRT_K_BVHW;
-                    r.a = root;
-                }
-        if (!leaves_ok) return mrt_internal_fail(MRT_ERR_INVALID, "bvh_node leaf outside the device encoding (> 127 primitives or > 2^24 leaf records)");
-    }
-    {  // treelet kernels cache the first nodes of the wide array: the top levels
-        std::vector<uint32_t*> broots;
-        for (mrt_node& n : nodes)
-            if ((n.kind & 0xFF) == MRT_K_BVHW) broots.push_back(&n.a);
-        bfs_order(bwide, broots, BVHW_LEAF);
-    }
-    GraphCheck gc{nodes, v};
-    // stack words: one per level for the binary walk
-    gc.bvhw_depth = bvhw_depth;
-    gc.walk(v->root, 0, 0, false, 0);
-    if (!gc.ok) return mrt_internal_fail(MRT_ERR_INVALID, gc.why.c_str());
-    if (v->biased != MRT_NONE) {
-        if (v->biased >= nodes.size()) return mrt_internal_fail(MRT_ERR_INVALID, "bad biased node");
-        const mrt_node& b = nodes[v->biased];
-        if ((b.kind & 0xFF) == MRT_K_LIST)
-            for (uint32_t i = 0; i < b.b; i++)
-                if ((nodes[v->children[b.a + i]].kind & 0xFF) == MRT_K_LIST)
-                    return mrt_internal_fail(MRT_ERR_INVALID, "nested biased object_list");
-    }
-    std::vector<DMat> dmats(v->n_materials);
-    for (uint32_t i = 0; i < v->n_materials; i++) {
-        const mrt_material& m = v->materials[i];
-        DMat& d = dmats[i];
-        d.kind = m.kind;
-        d.tex = m.tex;
-        d.p = m.p;
-        d.flags = 0;
-        if (m.tex < v->n_textures && v->textures[m.tex].kind == MRT_T_COLOR) {
-            d.flags = DMAT_COLOR;
-            for (int k = 0; k < 4; k++) d.col[k] = v->textures[m.tex].f[k];
-        }
-        if (m.kind == MRT_M_DIELECTRIC) {  // dielectric::scatter's per-material quotients (material.h:121-175)
-            const float ref = m.p;
-            d.col[0] = 1.0f / ref;
-            float r0 = (1 - ref) / (1 + ref);
-            d.col[1] = r0 * r0;
-        }
-    }
-    // scene.biased_objects flattened: an object_list's children, or the object itself
-    std::vector<mrt_node> bleaf;
-    uint32_t blist = 0;
-    if (v->biased != MRT_NONE) {
-        const mrt_node& b = nodes[v->biased];
-        if ((b.kind & 0xFF) == MRT_K_LIST) {
-            blist = 1;
-            for (uint32_t i = 0; i < b.b; i++) bleaf.push_back(nodes[v->children[b.a + i]]);
-        } else {
-            bleaf.push_back(b);
-        }
-    }
-    for (const mrt_node& l : bleaf)
-        if ((l.kind & 0xFF) != MRT_K_XZ && (l.kind & 0xFF) != MRT_K_SPHERE) T->blazy = 1;
-    if (bleaf.empty()) bleaf.push_back(mrt_node{});
-    LinCompiler lc{nodes, v, {}};
-    const char* force_generic = getenv("MRT_FORCE_GENERIC");  // test hook: run the generic machine
-    const bool lin = !(force_generic && *force_generic && *force_generic != '0') && lc.emit(v->root, 0, 0, 0);
-    if (!lin) lc.prog.clear();
-    T->prog_ops = (uint32_t)lc.prog.size();
-    lc.prog.push_back(LinOp{});  // LOP_END
-    T->features = scene_features(v, nodes, absorbed);
-    const char* no_sig = getenv("MRT_NO_SIG");  // test hook: run the interpreter on known shapes too
-    if (lin) T->features |= FT_LIN;
-    if (lin && lc.vsub) T->features |= FT_VSUB;
-    if (lin) cornell_room_fill(lc.prog.data(), (uint32_t)lc.prog.size());  // (Cornell shape: the room into the END op)
-    if (lin && !(no_sig && *no_sig && *no_sig != '0')) T->features |= MRT_SIG_BITS(lin_sig_of(lc.prog.data(), (uint32_t)lc.prog.size()));
-    // the Cornell walk tests op 3 (the light) once per ray; the same test serves xz_rect::pdf_value where
-    // the biased list is that one rect: same bounds, plane and side, bit for bit
-    T->light_once = (lin && MRT_SIG_OF(T->features) == SIG_CORNELL && v->biased != MRT_NONE && bleaf.size() == 1 &&
-                     (bleaf[0].kind & 0xFF) == MRT_K_XZ && memcmp(bleaf[0].f, lc.prog[3].f, 6 * sizeof(float)) == 0)
-                        ? 1u : 0u;
-    T->nbleaf = blist ? nodes[v->biased].b : 1u;
-    T->blist = blist;
-    T->max_frames = gc.max_frames;
-    T->max_rays = gc.max_rays;
-    T->max_mesh = gc.max_mesh;
-    T->nodes.swap(nodes);
-    T->wide.swap(wide);
-    T->bwide.swap(bwide);
-    T->bprims.swap(bprims);
-    T->dmats.swap(dmats);
-    T->bleaf.swap(bleaf);
-    if (lin) T->prog_fast = lin_rewrite_fast(lc.prog);
-    T->prog.swap(lc.prog);
-    return MRT_OK;
-}
-
 extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_scene** out) {
     if (!out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_scene_upload: null");
     if (device == MRT_DEVICE_CPU) {  // the CPU backend (explicit choice only)
@@ -1052,10 +483,12 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
     mrt_status st = mrt_internal_scene_tables(v, &T);
     if (st) return st;
     HIPCHK(hipSetDevice(device));
-    mrt_scene* s = new mrt_scene();
+    // owned until *out takes it: every early return below frees the scene and what it has uploaded
+    std::unique_ptr<mrt_scene, decltype(&mrt_scene_free)> owner(new mrt_scene(), mrt_scene_free);
+    mrt_scene* const s = owner.get();
     s->device = device;
     DScene& S = s->S;
-#define UP(src, n, dst) { void* t_ = nullptr; if ((st = upload(s, src, (size_t)(n) * sizeof(*(src)), &t_))) { mrt_scene_free(s); return st; } *(dst) = (decltype(+*(dst)))t_; }
+#define UP(src, n, dst) { void* t_ = nullptr; if ((st = upload(s, src, (size_t)(n) * sizeof(*(src)), &t_))) return st; *(dst) = (decltype(+*(dst)))t_; }
     UP(T.nodes.data(), T.nodes.size(), &S.nodes);
     UP(v->children, v->n_children, &S.children);
     UP(v->mesh_nodes, v->n_mesh_nodes, &S.mnodes);
@@ -1091,9 +524,9 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
     s->n_nodes = v->n_nodes;
     s->prog_ops = T.prog_ops;
     void* p;
-    if ((st = upload(s, &s->S, sizeof(DScene), &p))) { mrt_scene_free(s); return st; }
+    if ((st = upload(s, &s->S, sizeof(DScene), &p))) return st;
     s->d_S = (DScene*)p;
-    if ((st = dev_alloc(s, &p, 64))) { mrt_scene_free(s); return st; }
+    if ((st = dev_alloc(s, &p, 64))) return st;
     s->d_counter = (uint64_t*)p;
     s->d_rays = (unsigned long long*)((char*)p + 16);
     HIPCHK(hipMemset(p, 0, 64));  // the cancel flag (d_counter + 4) starts clear
@@ -1114,7 +547,6 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
             s->walk_min = (uint32_t)atoi(e);
             walk_min_env = true;
         }
-    const std::vector<BvhWide>& bwide = T.bwide;
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     s->n_cu = (uint32_t)prop.multiProcessorCount;
@@ -1130,7 +562,6 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
         const uint32_t waves_per_wg = L.wg / 64u;
         // the Cornell walk of the tolerance contract (mrt_sig.h cornell_fast_hit) parks no ray
         L.lds_save = tabs[k]->box6_walk[s->variant] ? 0u : s->lds_save;
-        L.lds_mesh = s->lds_mesh;
         L.rewrite = tabs[k]->rewrite[s->variant] != 0;
         L.retrace = tabs[k]->retrace[s->variant];
         // a fast-arithmetic kernel hands its rounding-critical paths to the exact arithmetic
@@ -1139,7 +570,6 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
             const char* e = getenv("MRT_RETRACE");
             L.handover = k == 1 && L.retrace && L.fn != kernel_table_fast_pex().kernel[s->variant] && !(e && *e && atoi(e) == 0);
         }
-        L.retrace_lds = (size_t)64 * 4 * (s->lds_frames * 2 + s->lds_rays * 11 + s->lds_mesh + s->lds_save);
         // the path-exact build (the metal bunny under the tolerance contract) yields at 32 walking
         // lanes: 40 -1.2%, 28 -1.7%, 48 -10% (bunny 1024x1024x64, profiles/r04_ab.txt section 13)
         L.walk_min = (!walk_min_env && L.fn == kernel_table_fast_pex().kernel[s->variant]) ? 32u : s->walk_min;
@@ -1148,20 +578,14 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
         const int vg = std::max(8, (fa.numRegs + 7) & ~7);
         const int nb_vgpr = std::max(1, std::min(8, 512 / vg) * 4 / (int)waves_per_wg);  // waves per CU / waves per group
         auto groups = [&](size_t lds) { return std::max(1, lds ? std::min<int>(nb_vgpr, (int)((160u * 1024u) / lds)) : nb_vgpr); };
-        const size_t lds_core = (size_t)waves_per_wg * 64 * 4 *
-                                (s->lds_frames * 2 + s->lds_rays * 11 + L.lds_mesh + L.lds_save + tabs[k]->lev_k[s->variant] * 4 +
-                                 tabs[k]->pq[s->variant]);
-        L.lds_bytes = lds_core;
-        if (L.lds_bytes > (size_t)prop.sharedMemPerBlock) {
-            mrt_scene_free(s);
-            return mrt_internal_fail(MRT_ERR_INVALID, "scene graph too deep for the LDS stacks");
-        }
+        L.lds_bytes = (size_t)waves_per_wg * 64 * 4 * (lds_stack_words(s, L.lds_save) + tabs[k]->lev_k[s->variant] * 4 + tabs[k]->pq[s->variant]);
+        if (L.lds_bytes > (size_t)prop.sharedMemPerBlock) return mrt_internal_fail(MRT_ERR_INVALID, "scene graph too deep for the LDS stacks");
         int nb = groups(L.lds_bytes);
         if (tabs[k]->tree[s->variant]) {
             // the LDS the resident groups leave free, split among them: the treelet of each group
             const size_t per = std::min<size_t>((160u * 1024u) / nb, (size_t)prop.sharedMemPerBlock);
             const uint32_t node_bytes = 64u;  // BvhWide
-            const uint32_t n_nodes = (uint32_t)bwide.size();
+            const uint32_t n_nodes = (uint32_t)T.bwide.size();
             uint32_t cap = per > L.lds_bytes ? (uint32_t)((per - L.lds_bytes) / node_bytes) : 0u;
 #ifdef MRT_EXPERIMENTS
             if (const char* e = getenv("MRT_TREELET_NODES"))  // sweep hook
@@ -1181,7 +605,7 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
         if (L.grid < (int)MRT_NPART) return mrt_internal_fail(MRT_ERR_HIP, "path kernel grid smaller than the work partitions");
         s->max_threads = std::max(s->max_threads, (size_t)L.grid * L.wg);
     }
-    *out = s;
+    *out = owner.release();
     return MRT_OK;
 }
 
@@ -1207,10 +631,7 @@ extern "C" void mrt_scene_free(mrt_scene* s) {
     if (s->fstream) (void)hipStreamDestroy(s->fstream);
     for (hipEvent_t e : {s->ev_kern, s->ev_fold[0], s->ev_fold[1]})
         if (e) (void)hipEventDestroy(e);
-    for (void* p : {(void*)s->d_rad2, (void*)s->d_counters, (void*)s->d_pixels, (void*)s->d_sdist, (void*)s->d_rad, (void*)s->d_path_rays, (void*)s->d_acc,
-                    (void*)s->d_lev, (void*)s->d_out, (void*)s->d_prev, (void*)s->d_rt})
-        if (p) (void)hipFree(p);
-    delete s;
+    delete s;  // (the workspace buffers release themselves: DevBuf)
 }
 
 static uint32_t auto_chunk(uint32_t npix, uint32_t ns) {
@@ -1241,16 +662,15 @@ static mrt_status quiesce(mrt_scene* s) {
     }
     return MRT_OK;
 }
-static mrt_status grow(mrt_scene* s, void** p, size_t* cap, size_t bytes) {
-    if (*cap >= bytes && *p) return MRT_OK;
+template <typename T>
+mrt_status DevBuf<T>::grow(mrt_scene* s, size_t bytes) {
+    if (cap >= bytes && p) return MRT_OK;
     mrt_status st = quiesce(s);
     if (st) return st;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    release();
+    hipError_t e = hipMalloc((void**)&p, bytes ? bytes : 16);
     if (e != hipSuccess) return mrt_internal_fail(MRT_ERR_OOM, "workspace allocation failed");
-    *cap = bytes;
+    cap = bytes;
     return MRT_OK;
 }
 
@@ -1288,8 +708,8 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
         std::vector<uint2> xy(px.size());
         for (size_t i = 0; i < px.size(); i++) xy[i] = make_uint2(px[i] % d->width, px[i] / d->width);
         if ((st = quiesce(s))) return st;
-        if ((st = grow(s, (void**)&s->d_pixels, &s->px_cap, xy.size() * 8))) return st;
-        HIPCHK(hipMemcpy(s->d_pixels, xy.data(), xy.size() * 8, hipMemcpyHostToDevice));
+        if ((st = s->d_pixels.grow(s, xy.size() * 8))) return st;
+        HIPCHK(hipMemcpy(s->d_pixels.p, xy.data(), xy.size() * 8, hipMemcpyHostToDevice));
         s->npix = (uint32_t)px.size();
     }
     if (s->sdist_sq != d->sqrt_samples) {  // sample grid of main.cpp:319-332, in float like the reference
@@ -1299,8 +719,8 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
             for (uint32_t j = 0; j < sq; j++)
                 sd[(size_t)i * sq + j] = make_float2(((float)i + 0.5f) / (float)sq, ((float)j + 0.5f) / (float)sq);
         if ((st = quiesce(s))) return st;
-        if ((st = grow(s, (void**)&s->d_sdist, &s->sd_cap, sd.size() * 8))) return st;
-        HIPCHK(hipMemcpy(s->d_sdist, sd.data(), sd.size() * 8, hipMemcpyHostToDevice));
+        if ((st = s->d_sdist.grow(s, sd.size() * 8))) return st;
+        HIPCHK(hipMemcpy(s->d_sdist.p, sd.data(), sd.size() * 8, hipMemcpyHostToDevice));
         s->sdist_sq = sq;
     }
     uint32_t chunk = d->chunk_samples ? std::min(d->chunk_samples, ns) : auto_chunk(s->npix, ns);
@@ -1312,11 +732,11 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
     if (chunk != s->chunk && (st = quiesce(s))) return st;  // the fold of a running render reads `chunk` rows
     s->chunk = chunk;
     size_t paths = (size_t)s->npix * s->chunk;
-    if ((st = grow(s, (void**)&s->d_rad, &s->rad_cap, paths * 12))) return st;
+    if ((st = s->d_rad.grow(s, paths * 12))) return st;
     if (d->flags & MRT_RF_FOLD_ASYNC) {
         if (d->flags & (MRT_RF_PREVIEW | MRT_RF_PATH_DEBUG | MRT_RF_FOLD_BEHIND))
             return mrt_internal_fail(MRT_ERR_INVALID, "MRT_RF_FOLD_ASYNC: no preview, debug or lean fold");
-        if ((st = grow(s, (void**)&s->d_rad2, &s->rad2_cap, paths * 12))) return st;
+        if ((st = s->d_rad2.grow(s, paths * 12))) return st;
         if (!s->fstream) HIPCHK(hipStreamCreateWithFlags(&s->fstream, hipStreamNonBlocking));
         if (!s->ev_kern) HIPCHK(hipEventCreateWithFlags(&s->ev_kern, hipEventDisableTiming));
         for (hipEvent_t& e : s->ev_fold)
@@ -1324,12 +744,12 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
     }
     // (two lists: one per radiance parity of the async fold)
     if ((d->flags & MRT_RF_FAST) && !(d->flags & MRT_RF_PATH_DEBUG) && s->pl[1].handover &&
-        (st = grow(s, (void**)&s->d_rt, &s->rt_cap, (size_t)2 * kRtCap * sizeof(uint32_t))))
+        (st = s->d_rt.grow(s, (size_t)2 * kRtCap * sizeof(uint32_t))))
         return st;
-    if ((st = grow(s, (void**)&s->d_acc, &s->acc_cap, (size_t)s->npix * 16))) return st;
-    if ((st = grow(s, (void**)&s->d_out, &s->out_cap, (size_t)s->npix * 16 + 16))) return st;
+    if ((st = s->d_acc.grow(s, (size_t)s->npix * 16))) return st;
+    if ((st = s->d_out.grow(s, (size_t)s->npix * 16 + 16))) return st;
     if (d->flags & MRT_RF_PREVIEW) {
-        if ((st = grow(s, (void**)&s->d_prev, &s->prev_cap, (size_t)s->npix * 16 + 16))) return st;
+        if ((st = s->d_prev.grow(s, (size_t)s->npix * 16 + 16))) return st;
         std::lock_guard<std::mutex> lk(s->prog_mu);
         if (s->h_prev_cap < s->npix) {
             if ((st = quiesce(s))) return st;
@@ -1350,9 +770,9 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
         s->prev_h = d->height;
     }
     if (d->flags & MRT_RF_PATH_DEBUG)
-        if ((st = grow(s, (void**)&s->d_path_rays, &s->pr_cap, paths * 4))) return st;
+        if ((st = s->d_path_rays.grow(s, paths * 4))) return st;
     s->lev_rows = std::max<uint32_t>(d->max_bounces, 1);
-    if ((st = grow(s, (void**)&s->d_lev, &s->lev_cap, (size_t)s->lev_rows * s->max_threads * 16))) return st;
+    if ((st = s->d_lev.grow(s, (size_t)s->lev_rows * s->max_threads * 16))) return st;
     // Two sets of counter slots / progress snapshots, `slot_half` launches each, at FIXED offsets 0
     // and slot_half: consecutive MRT_RF_FOLD_ASYNC renders alternate between them, because a render's
     // last fold still resets its set while the next render's kernels count in the other.  The stride
@@ -1366,10 +786,11 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
     const uint32_t launches = 2 * half;
     const size_t cnt_words = (size_t)MRT_CNT_SLOTS * MRT_COUNTER_STRIDE;  // per launch
     {
-        void* const before = s->d_counters;
-        if ((st = grow(s, (void**)&s->d_counters, &s->cnt_cap, (size_t)launches * cnt_words * 8))) return st;
+        const size_t bytes = (size_t)launches * cnt_words * 8;
+        const bool kept = s->d_counters.p && s->d_counters.cap >= bytes;
+        if ((st = s->d_counters.grow(s, bytes))) return st;
         // zeroed once at allocation; afterwards every render's final kernel leaves them zero
-        if (s->d_counters != before) HIPCHK(hipMemset(s->d_counters, 0, s->cnt_cap));
+        if (!kept) HIPCHK(hipMemset(s->d_counters.p, 0, s->d_counters.cap));
     }
     if (!s->pstream) HIPCHK(hipStreamCreateWithFlags(&s->pstream, hipStreamNonBlocking));
     if (!s->ev_done) HIPCHK(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
@@ -1404,6 +825,30 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
     if (d->pixels) s->wdesc.pixels = s->wpixels.data();
     s->have_ws = true;
     return MRT_OK;
+}
+
+// What a render launch and the aux launch share of PathParams (after mrt_prepare): the scene, the
+// build's LDS stack words, the pixel table and the sample grid, the image and the path streams.
+static PathParams launch_params(const mrt_scene* s, const PathLaunch& PL, const mrt_render_desc* d) {
+    PathParams P{};
+    P.sc = s->S;
+    P.lds_frames = s->lds_frames;
+    P.lds_rays = s->lds_rays;
+    P.lds_mesh = s->lds_mesh;
+    P.lds_save = PL.lds_save;
+    P.pixels = s->d_pixels.p;
+    P.sdist = s->d_sdist.p;
+    P.npix = s->npix;
+    P.inv_npix = 1.0 / (double)std::max<uint32_t>(s->npix, 1);
+    P.width = d->width;
+    P.height = d->height;
+    P.inv_w = 1.0f / (float)d->width;
+    P.inv_h = 1.0f / (float)d->height;
+    P.fast_uv = 1;  // checked by mrt_prepare (and sq < 2^16 since sq^2 fits in 32 bits)
+    P.sq = d->sqrt_samples;
+    P.ns = d->sqrt_samples * d->sqrt_samples;
+    P.seed = d->seed;
+    return P;
 }
 
 extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, float* d_local, uint64_t* d_rays, void* stream) {
@@ -1445,7 +890,7 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
         std::lock_guard<std::mutex> lk(s->prog_mu);
         s->prog_base = rpar * s->slot_half;
     }
-    unsigned long long* const d_cnt = (unsigned long long*)(s->d_counters + (size_t)rpar * s->slot_half * MRT_CNT_SLOTS * MRT_COUNTER_STRIDE);
+    unsigned long long* const d_cnt = (unsigned long long*)(s->d_counters.p + (size_t)rpar * s->slot_half * MRT_CNT_SLOTS * MRT_COUNTER_STRIDE);
     unsigned long long* const h_prog = (unsigned long long*)(s->h_prog + (size_t)rpar * s->slot_half * MRT_NPART);
     uint32_t seq = 0;
     if (preview) {  // a new render: no snapshot yet (sequence 0), in stream order
@@ -1465,30 +910,14 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
             s->lpar ^= 1u;
             if (s->fold_pending[par]) HIPCHK(hipStreamWaitEvent(q, s->ev_fold[par], 0));
         }
-        float* const d_rad = par ? s->d_rad2 : s->d_rad;
-        PathParams P{};
-        P.sc = s->S;
+        float* const d_rad = par ? s->d_rad2.p : s->d_rad.p;
+        PathParams P = launch_params(s, PL, d);
         // the interpreter's tolerance-contract program (rooms and box.h lists as slab tests); the
         // shape-specialised walks read the program as compiled
         if ((d->flags & MRT_RF_FAST) && s->prog_fast && PL.rewrite) P.sc.prog = s->prog_fast;
-        P.lds_frames = s->lds_frames;
-        P.lds_rays = s->lds_rays;
-        P.lds_mesh = PL.lds_mesh;
-        P.lds_save = PL.lds_save;
         P.walk_min = PL.walk_min;
         P.tree_src = reinterpret_cast<const float4*>(s->S.bwide);
         P.tree_n = PL.tree_n;
-        P.pixels = s->d_pixels;
-        P.sdist = s->d_sdist;
-        P.npix = s->npix;
-        P.inv_npix = 1.0 / (double)std::max<uint32_t>(s->npix, 1);
-        P.width = d->width;
-        P.height = d->height;
-        P.inv_w = 1.0f / (float)d->width;
-        P.inv_h = 1.0f / (float)d->height;
-        P.fast_uv = 1;  // checked by mrt_prepare (and sq < 2^16 since sq^2 fits in 32 bits)
-        P.sq = d->sqrt_samples;
-        P.ns = ns;
         P.s0 = s0;
         P.n_paths = s->npix * (s1 - s0);
         P.tail_zone = (uint32_t)std::min<uint64_t>((uint64_t)grid * (PL.wg / 64u) * 2 * MRT_BATCH, P.n_paths);  // ~2 big claims per wave
@@ -1500,20 +929,19 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
             const uint64_t waves_k = (uint64_t)((grid - k + MRT_NPART - 1) / MRT_NPART) * (PL.wg / 64u);
             P.part_dyn[k] = P.part_base[k] + (P.static_first ? waves_k * MRT_BATCH : 0);
         }
-        P.seed = d->seed;
         P.max_bounces = d->max_bounces;
         P.rad = d_rad;
-        P.path_rays = (d->flags & MRT_RF_PATH_DEBUG) ? s->d_path_rays : nullptr;
+        P.path_rays = (d->flags & MRT_RF_PATH_DEBUG) ? s->d_path_rays.p : nullptr;
         P.counter = d_cnt + (size_t)s->n_launch * MRT_CNT_SLOTS * MRT_COUNTER_STRIDE;
         P.hprog = h_prog + (size_t)s->n_launch * MRT_NPART;
         P.cancel = (const int*)(s->d_counter + 4);
         P.rays = d_rays ? (unsigned long long*)d_rays : s->d_rays;
-        P.lev = s->d_lev;
+        P.lev = s->d_lev.p;
         P.lev_rows = s->lev_rows;
         // the list of the launch's radiance parity: entries at par * kRtCap, its count and its groups-done
         // word at d_counter[1] / [3] (parity 0) or the two halves of d_counter[6] (parity 1)
         if (handover)
-            P.rt = RetraceList{s->d_rt + (size_t)par * kRtCap, par ? (uint32_t*)(s->d_counter + 6) : (uint32_t*)(s->d_counter + 1), kRtCap,
+            P.rt = RetraceList{s->d_rt.p + (size_t)par * kRtCap, par ? (uint32_t*)(s->d_counter + 6) : (uint32_t*)(s->d_counter + 1), kRtCap,
                                par ? (uint32_t*)(s->d_counter + 6) + 1 : (uint32_t*)(s->d_counter + 3), (unsigned long long*)s->d_counter,
                                (unsigned long long*)(s->d_counter + 5)};
         HIPCHK(hipEventRecord(s->ev[2 * s->n_launch], q));
@@ -1527,18 +955,20 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
         if (handover) {
             PathParams PR = P;
             PR.sc.prog = s->S.prog;
-            hipLaunchKernelGGL(PL.retrace, dim3(kRetraceGroups), dim3(64), PL.retrace_lds, q, PR);
+            hipLaunchKernelGGL(PL.retrace, dim3(kRetraceGroups), dim3(64), (size_t)64 * 4 * lds_stack_words(s, s->lds_save), q, PR);
             HIPCHK(hipGetLastError());
         }
+        // the last chunk's full fold finishes the render (no preview: no snapshot of acc needed;
+        // the 8-VGPR lean fold cannot take the division as well: a final kernel follows it); an
+        // MRT_RF_FOLD_ASYNC render has neither preview nor lean fold (mrt_prepare)
+        const bool lean = (d->flags & MRT_RF_FOLD_BEHIND) && d->mode == 0;
+        const bool last = s1 == ns && !preview && !lean;
+        const FoldEnd fe{last ? (float4*)d_local : nullptr, ns, last ? d_cnt : nullptr, last ? h_prog : nullptr,
+                         last ? launches * MRT_CNT_SLOTS : 0u, last ? launches * MRT_NPART : 0u};
         if (async) {  // the fold on the fold stream, beside the next launch's path kernel
             HIPCHK(hipEventRecord(s->ev_kern, q));
             HIPCHK(hipStreamWaitEvent(s->fstream, s->ev_kern, 0));
-        }
-        if (async) {  // the fold beside the next launch's path kernel
-            const bool last = s1 == ns;
-            FoldEnd fe{last ? (float4*)d_local : nullptr, ns, last ? d_cnt : nullptr, last ? h_prog : nullptr,
-                       last ? launches * MRT_CNT_SLOTS : 0u, last ? launches * MRT_NPART : 0u};
-            hipLaunchKernelGGL(mrt_fold_async_kernel, dim3(s->n_cu * MRT_FOLD_ASYNC_GROUPS), dim3(MRT_FOLD_ASYNC_WG), 0, s->fstream, d_rad, s->d_acc, s->npix,
+            hipLaunchKernelGGL(mrt_fold_async_kernel, dim3(s->n_cu * MRT_FOLD_ASYNC_GROUPS), dim3(MRT_FOLD_ASYNC_WG), 0, s->fstream, d_rad, s->d_acc.p, s->npix,
                                s0, s1, d->mode, d->max_luminance, fe);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(s->ev_fold[par], s->fstream));
@@ -1546,27 +976,21 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
             s->last_paths = P.n_paths;
             continue;
         }
-        // the last chunk's full fold finishes the render (no preview: no snapshot of acc needed;
-        // the 8-VGPR lean fold cannot take the division as well: a final kernel follows it)
-        const bool lean = (d->flags & MRT_RF_FOLD_BEHIND) && d->mode == 0;
-        const bool last = s1 == ns && !preview && !lean;
-        FoldEnd fe{last ? (float4*)d_local : nullptr, ns, last ? (unsigned long long*)s->d_counters : nullptr,
-                   last ? (unsigned long long*)s->h_prog : nullptr, last ? launches * MRT_CNT_SLOTS : 0u, last ? launches * MRT_NPART : 0u};
         const uint32_t nthr = std::max(s->npix, fe.nreset);
         if (lean)
             hipLaunchKernelGGL(mrt_fold_lean_kernel, dim3((s->npix + MRT_FOLD_LEAN_WG - 1) / MRT_FOLD_LEAN_WG), dim3(MRT_FOLD_LEAN_WG), 0, q,
-                               d_rad, s->d_acc, s->npix, s1 - s0, (uint32_t)(s0 == 0));
+                               d_rad, s->d_acc.p, s->npix, s1 - s0, (uint32_t)(s0 == 0));
         else
-            hipLaunchKernelGGL(mrt_fold_kernel, dim3((nthr + 255) / 256), dim3(256), 0, q, d_rad, s->d_acc, s->npix, s0, s1, d->mode,
+            hipLaunchKernelGGL(mrt_fold_kernel, dim3((nthr + 255) / 256), dim3(256), 0, q, d_rad, s->d_acc.p, s->npix, s0, s1, d->mode,
                                d->max_luminance, fe);
         HIPCHK(hipGetLastError());
         if (preview) {  // the image after s1 samples, copied under the sequence lock
-            hipLaunchKernelGGL(mrt_final_kernel, dim3((s->npix + MRT_FINAL_WG - 1) / MRT_FINAL_WG), dim3(MRT_FINAL_WG), 0, q, s->d_acc, s->d_prev,
+            hipLaunchKernelGGL(mrt_final_kernel, dim3((s->npix + MRT_FINAL_WG - 1) / MRT_FINAL_WG), dim3(MRT_FINAL_WG), 0, q, s->d_acc.p, s->d_prev.p,
                                s->npix, s1, d->mode, d->max_luminance,
                                (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0u, 0u);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamWriteValue32(q, s->h_seq, 2 * seq + 1, 0));
-            HIPCHK(hipMemcpyAsync(s->h_prev, s->d_prev, (size_t)s->npix * 16, hipMemcpyDeviceToHost, q));
+            HIPCHK(hipMemcpyAsync(s->h_prev, s->d_prev.p, (size_t)s->npix * 16, hipMemcpyDeviceToHost, q));
             HIPCHK(hipStreamWriteValue32(q, s->h_seq + 1, s1, 0));
             HIPCHK(hipStreamWriteValue32(q, s->h_seq, 2 * seq + 2, 0));
             seq++;
@@ -1576,8 +1000,8 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
     if (preview || ((d->flags & MRT_RF_FOLD_BEHIND) && d->mode == 0)) {  // (otherwise the last fold wrote the output and reset the counters)
         const uint32_t nreset = launches * MRT_CNT_SLOTS;
         const uint32_t blocks = (std::max(s->npix, nreset) + MRT_FINAL_WG - 1) / MRT_FINAL_WG;
-        hipLaunchKernelGGL(mrt_final_kernel, dim3(blocks), dim3(MRT_FINAL_WG), 0, q, s->d_acc, (float4*)d_local, s->npix, ns, d->mode,
-                           d->max_luminance, (unsigned long long*)s->d_counters, (unsigned long long*)s->h_prog, nreset, launches * MRT_NPART);
+        hipLaunchKernelGGL(mrt_final_kernel, dim3(blocks), dim3(MRT_FINAL_WG), 0, q, s->d_acc.p, (float4*)d_local, s->npix, ns, d->mode,
+                           d->max_luminance, d_cnt, h_prog, nreset, launches * MRT_NPART);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(s->ev_done, async ? s->fstream : q));
@@ -1600,7 +1024,7 @@ extern "C" mrt_status mrt_render(mrt_scene* s, const mrt_render_desc* d, float* 
     mrt_status st = mrt_prepare(s, d);
     if (st) return st;
     HIPCHK(hipMemset(s->d_rays, 0, 8));
-    st = mrt_render_device(s, d, (float*)s->d_out, (uint64_t*)s->d_rays, nullptr);
+    st = mrt_render_device(s, d, (float*)s->d_out.p, (uint64_t*)s->d_rays, nullptr);
     if (st) return st;
     // wait, forwarding the caller's cancel flag to the device flag the path kernel polls
     bool cancelled = false;
@@ -1623,7 +1047,7 @@ extern "C" mrt_status mrt_render(mrt_scene* s, const mrt_render_desc* d, float* 
     if (cancelled) HIPCHK(hipMemset(s->d_counter + 4, 0, 8));  // the render is over: clear the flag for the next one
     std::vector<float> local((size_t)s->npix * 4);
     std::vector<uint32_t> px = mrt_internal_local_pixels(d);
-    HIPCHK(hipMemcpy(local.data(), s->d_out, local.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(local.data(), s->d_out.p, local.size() * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < px.size(); i++) memcpy(rgb_out + (size_t)px[i] * 4, &local[i * 4], 16);
     uint64_t rays = 0;
     HIPCHK(hipMemcpy(&rays, s->d_rays, 8, hipMemcpyDeviceToHost));
@@ -1656,25 +1080,8 @@ extern "C" mrt_status mrt_render_aux_device(mrt_scene* s, const mrt_render_desc*
     if (s->npix == 0) return MRT_OK;
     const aux_kernel_t fn = aux_kernel_table().kernel[s->variant];
     const PathLaunch& PL = s->pl[0];  // the exact build's stack sizes
-    PathParams P{};
-    P.sc = s->S;
-    P.lds_frames = s->lds_frames;
-    P.lds_rays = s->lds_rays;
-    P.lds_mesh = PL.lds_mesh;
-    P.lds_save = PL.lds_save;
-    P.pixels = s->d_pixels;
-    P.sdist = s->d_sdist;
-    P.npix = s->npix;
-    P.inv_npix = 1.0 / (double)s->npix;
-    P.width = d->width;
-    P.height = d->height;
-    P.inv_w = 1.0f / (float)d->width;
-    P.inv_h = 1.0f / (float)d->height;
-    P.fast_uv = 1;
-    P.sq = d->sqrt_samples;
-    P.ns = d->sqrt_samples * d->sqrt_samples;
-    P.seed = d->seed;
-    const size_t lds_bytes = (size_t)64 * 4 * (P.lds_frames * 2 + P.lds_rays * 11 + P.lds_mesh + P.lds_save);
+    const PathParams P = launch_params(s, PL, d);
+    const size_t lds_bytes = (size_t)64 * 4 * lds_stack_words(s, PL.lds_save);
     hipStream_t q = (hipStream_t)stream;
     hipLaunchKernelGGL(fn, dim3((s->npix + 63u) / 64u), dim3(64), lds_bytes, q, P, (float4*)d_normal, (float4*)d_albedo);
     HIPCHK(hipGetLastError());
@@ -1734,8 +1141,8 @@ extern "C" mrt_status mrt_render_debug(mrt_scene* s, float* path_rgb, uint32_t* 
     if (!s || !(s->wdesc.flags & MRT_RF_PATH_DEBUG) || n_paths != s->last_paths)
         return mrt_internal_fail(MRT_ERR_INVALID, "mrt_render_debug: no debug render of that size");
     HIPCHK(hipSetDevice(s->device));
-    if (path_rgb) HIPCHK(hipMemcpy(path_rgb, s->d_rad, n_paths * 12, hipMemcpyDeviceToHost));
-    if (path_rays) HIPCHK(hipMemcpy(path_rays, s->d_path_rays, n_paths * 4, hipMemcpyDeviceToHost));
+    if (path_rgb) HIPCHK(hipMemcpy(path_rgb, s->d_rad.p, n_paths * 12, hipMemcpyDeviceToHost));
+    if (path_rays) HIPCHK(hipMemcpy(path_rays, s->d_path_rays.p, n_paths * 4, hipMemcpyDeviceToHost));
     return MRT_OK;
 }
 

@@ -1,6 +1,7 @@
-// mrt_tables.h -- the device-side scene tables, built on the host from a mrt_scene_view
-// (mrt_render.hip) and used by both backends: the GPU uploads them to HBM (mrt_scene_upload), the
-// CPU backend keeps them in host memory (mrt_cpu.hip) and walks them with the same hot-path code.
+// mrt_tables.h -- the device-side scene tables, built on the host from a mrt_scene_view by the
+// scene compiler (mrt_tables.hip, host code only) and used by both backends: the GPU uploads them
+// to HBM (mrt_render.hip mrt_scene_upload), the CPU backend keeps them in host memory (mrt_cpu.hip)
+// and walks them with the same hot-path code.
 #pragma once
 #include <vector>
 #include "mrt_shade.h"
@@ -23,3 +24,6 @@ struct SceneTables {
     int max_frames = 0, max_rays = 0, max_mesh = 0;  // deepest stacks of the scene graph
 };
 mrt_status mrt_internal_scene_tables(const mrt_scene_view* v, SceneTables* t);
+// the tables as 17 words (mrt_debug_tables_digest; tools/tables_check.cpp)
+#define MRT_TABLES_DIGEST_WORDS 17
+void mrt_internal_tables_digest(const SceneTables& t, uint64_t d[MRT_TABLES_DIGEST_WORDS]);

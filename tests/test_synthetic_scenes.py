@@ -13,8 +13,8 @@ GPU leg            the kernel picked is the entry's literal; the exact contract 
                    force the other walks; the tolerance contract holds the bars
                    test_fast_numerics_close_to_exact_other_scenes uses.
 
-The feature / kernel literals are worked out by hand from scene_features and pick_variant
-(mrt_render.hip, mrt_launch.h kVariants): index 0-2 the shape-specialised walks, 3-7 the narrower
+The feature / kernel literals are worked out by hand from scene_features (mrt_tables.hip) and
+pick_variant (mrt_render.hip, mrt_launch.h kVariants): index 0-2 the shape-specialised walks, 3-7 the narrower
 interpreters, 8 the catch-all interpreter 0x3FFF, 9 the generic machine 0x37FF.
 """
 import ctypes as C
