@@ -17,7 +17,7 @@ CSRC     = miniraytracer_amd/csrc
 OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
-           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_denoise.o \
+           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
            $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
@@ -77,6 +77,12 @@ $(OBJDIR)/mrt_aux.o: $(CSRC)/mrt_aux.hip $(HDRS)
 $(OBJDIR)/mrt_denoise.o: $(CSRC)/mrt_denoise.hip include/mrt_denoise.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(if $(HOSTFMA),-Xarch_host $(HOSTFMA)) -c $< -o $@
+
+# the sample moments and the adaptive render's merge, host and device from include/mrt_adaptive.h:
+# no contraction on either side (HIPFLAGS); a translation unit of its own, like the two above
+$(OBJDIR)/mrt_adaptive.o: $(CSRC)/mrt_adaptive.hip include/mrt_adaptive.h $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)

@@ -15,6 +15,8 @@
  *   cancel                                G_isRunning                       main.cpp:54, 180, 235
  *   mrt_tonemap_argb                      Drago tone map + ARGB32            main.cpp:416-444, vec3.h:327-333
  *   mrt_lum_max_device/mrt_tonemap_device the same, on the device              main.cpp:421-442
+ *   mrt_render_adaptive / mrt_moments     (new) draw()'s fixed sample loop, per pixel as long as its
+ *                                         standard error asks                main.cpp:150-167
  *
  * Threading: one host thread per device; calls on distinct scenes are thread-safe, calls on the
  * same scene handle are not reentrant.
@@ -260,6 +262,53 @@ mrt_status mrt_denoise_device(const float* d_rgb, const float* d_normal, const f
                               const mrt_denoise_params* p, float* d_out, float* d_tmp, void* stream);
         /* whole row-major frames (e.g. after mrt_gather_frame, which moves any float4 shard); d_rgb is not
            written; d_out, d_tmp: W*H float4 each; enqueued, no sync, no allocation */
+
+/* ---- sample moments and the adaptive render ----------------------------------------------------
+ * (an addition; the reference spends the same samples on every pixel.)  Per pixel one float4 of
+ * moments m = (sum l, sum l^2, n_finite, N_spent) over its samples' luminance l, added in sample
+ * order in float32; the standard error of the pixel's mean and the refinement test built on it are
+ * include/mrt_adaptive.h's mrt_moments_se and mrt_moments_refine (one source for host and device:
+ * same bits).
+ *
+ * mrt_moments adds a radiance chunk in the render's per-path layout ([s][local pixel] float3, as
+ * mrt_render_debug returns it) to moments[slot], slot = slots[local pixel] (no repeats), or the
+ * local pixel itself when slots is NULL.  The caller zeroes `moments` first; a second call
+ * accumulates on top of the first, so the halves of a pixel's samples may come in two calls.
+ * MRT_ERR_INVALID: a null path_rgb / moments, or n_pixels * n_samples == 0. */
+mrt_status mrt_moments(const float* path_rgb, uint32_t n_pixels, uint32_t n_samples, const uint32_t* slots, float* moments);
+mrt_status mrt_moments_device(const float* d_path_rgb, uint32_t n_pixels, uint32_t n_samples, const uint32_t* d_slots, float* d_moments,
+                              void* stream);
+        /* GPU; device pointers (d_moments 16-byte aligned); enqueued on `stream`, nothing synchronised,
+           nothing allocated (capturable) */
+/* Host: refine_out[i] = mrt_moments_refine(moments[i], atol, rtol) (1 or 0) and, when se_out is not
+ * NULL, se_out[i] = mrt_moments_se(moments[i]) for n float4 moments -- the adaptive render's own
+ * decision, for callers that schedule samples themselves.  Either output may be NULL, not both. */
+mrt_status mrt_moments_decide(const float* moments, uint32_t n, float atol, float rtol, uint8_t* refine_out, float* se_out);
+
+/* The adaptive render.  Pass 0 is mrt_render of d as it stands (the same streams, kernels and
+ * fold), which also gathers every pixel's moments.  Pass k = 1 .. max_passes renders again, as a
+ * pixel list in ascending pass-0 local order, the pixels whose mrt_moments_refine(m, atol, rtol)
+ * holds -- on a grid twice as fine each pass (sqrt_samples * 2^k) and with the seed
+ * splitmix64(d->seed + k) (uint64 wrap), everything else from d -- and merges each finished pixel c
+ * of ns_k samples into the running colour C over N samples:
+ *   C = C + (c - C) * ((float)ns_k / (N + (float)ns_k)),  N = N + (float)ns_k   (float32, per channel)
+ * while the pixel's moments gain the pass's samples.  It stops early when no pixel refines.  A pixel
+ * that is never refined equals mrt_render's pixel bit for bit; max_passes = 0 is mrt_render plus the
+ * moments.  Every decision is per pixel, so ranks (d->rank / world) and pixel lists need nothing from
+ * each other, and both backends decide alike: their exact-contract results are the same bits.
+ *
+ * rgb_out, moments_out (may be NULL): W*H*4 floats, owned pixels only, like mrt_render;
+ * moments_out's w is the samples spent on the pixel.  rays_out: the sum over the passes.  cancel is
+ * handed to every pass and read between them.  Blocks like mrt_render; the host decides between the
+ * passes, so there is no device form and the call cannot be captured.
+ * Valid: max_passes <= 4; atol, rtol >= 0 and finite; d->mode == 0; d->flags 0 or MRT_RF_FAST; every
+ * pass's sqrt_samples^2 below 2^32.
+ * Defaults (mrt_default_adaptive_params; chosen on the Cornell box at a 16-spp base):
+ *   max_passes 2, atol 0.03, rtol 0 */
+typedef struct mrt_adaptive_params { uint32_t max_passes; float atol, rtol; } mrt_adaptive_params;
+void mrt_default_adaptive_params(mrt_adaptive_params* p);
+mrt_status mrt_render_adaptive(mrt_scene* s, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out,
+                               float* moments_out /* may be NULL */, uint64_t* rays_out, const volatile int* cancel);
 
 /* ---- multi-GPU: the framebuffer gather over RCCL (xGMI) ---------------------------------------
  * The reference's seam is main.cpp:347-382 (the worker threads over one work_queue) writing

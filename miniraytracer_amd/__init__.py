@@ -187,6 +187,19 @@ class Renderer:
         check(lib().mrt_render_aux_device(self._h, C.byref(desc), C.c_void_p(d_normal_ptr), C.c_void_p(d_albedo_ptr),
                                           C.c_void_p(stream_ptr)), "mrt_render_aux_device")
 
+    def render_adaptive(self, desc, params=None, cancel=None):
+        """Adaptive render (include/mrt.h mrt_render_adaptive), both backends: desc as the base pass, then
+        up to params.max_passes refinement passes over the pixels whose standard error misses
+        atol + rtol * mean.  Returns (img, moments, rays): float32 (H, W, 4) each -- moments = (sum l,
+        sum l^2, n_finite, samples spent) per pixel -- and the ray total of all passes."""
+        p = params if params is not None else default_adaptive_params()
+        img = np.zeros((desc.height, desc.width, 4), dtype=np.float32)
+        mom = np.zeros((desc.height, desc.width, 4), dtype=np.float32)
+        rays = C.c_uint64()
+        check(lib().mrt_render_adaptive(self._h, C.byref(desc), C.byref(p), img.ctypes.data, mom.ctypes.data, C.byref(rays),
+                                        C.byref(cancel) if cancel is not None else None), "mrt_render_adaptive")
+        return img, mom, rays.value
+
     def join(self, stream_ptr=0):
         """Order a HIP stream after this context's last render_device (its fold runs on the context's
         own stream under RF_FOLD_ASYNC): the worker threads' join() (main.cpp:490-493)."""
@@ -338,6 +351,69 @@ def denoise_device(d_rgb_ptr, d_normal_ptr, d_albedo_ptr, width, height, d_out_p
     p = params if params is not None else default_denoise_params()
     check(lib().mrt_denoise_device(C.c_void_p(d_rgb_ptr), C.c_void_p(d_normal_ptr), C.c_void_p(d_albedo_ptr), width, height,
                                    C.byref(p), C.c_void_p(d_out_ptr), C.c_void_p(d_tmp_ptr), C.c_void_p(stream_ptr)), "mrt_denoise_device")
+
+
+def default_adaptive_params(max_passes=None, atol=None, rtol=None):
+    """mrt_adaptive_params with the library's defaults (max_passes, atol, rtol), overridden where given."""
+    p = _lib.MrtAdaptiveParams()
+    lib().mrt_default_adaptive_params(C.byref(p))
+    if max_passes is not None:
+        p.max_passes = max_passes
+    if atol is not None:
+        p.atol = atol
+    if rtol is not None:
+        p.rtol = rtol
+    return p
+
+
+def moments(path_rgb, n_pixels, n_samples, slots=None, out=None):
+    """Per-pixel sample moments (include/mrt.h mrt_moments) of per-path radiance in the render's
+    layout ([s][local pixel] float3, as Renderer.paths returns it), on the host: (sum l, sum l^2,
+    n_finite, samples) per slot, slot = slots[local pixel] (no repeats) or the local pixel itself.
+    out: float32 (n, 4) moments to accumulate onto (returned); default zeros for n_pixels slots."""
+    rgb = np.ascontiguousarray(path_rgb, dtype=np.float32)
+    if rgb.size != n_pixels * n_samples * 3:
+        raise ValueError("moments: path_rgb must hold n_samples * n_pixels * 3 floats")
+    sl = None
+    if slots is not None:
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        if sl.size != n_pixels or len(np.unique(sl)) != n_pixels:
+            raise ValueError("moments: slots must hold n_pixels distinct indices")
+    if out is None:
+        out = np.zeros((n_pixels if sl is None else max(n_pixels, int(sl.max()) + 1), 4), dtype=np.float32)
+    if out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.size < 4 * (n_pixels if sl is None else int(sl.max()) + 1):
+        raise ValueError("moments: out must be a contiguous float32 array of (slots, 4)")
+    check(lib().mrt_moments(rgb.ctypes.data, n_pixels, n_samples, sl.ctypes.data if sl is not None else None, out.ctypes.data), "mrt_moments")
+    return out
+
+
+def moments_device(d_path_rgb_ptr, n_pixels, n_samples, d_moments_ptr, d_slots_ptr=0, stream_ptr=0):
+    """The same on the device (torch data_ptr()s), enqueued on a HIP stream: the chunk's samples are
+    added to the float4 moments at d_moments (zeroed by the caller before the first call)."""
+    check(lib().mrt_moments_device(C.c_void_p(d_path_rgb_ptr), n_pixels, n_samples, C.c_void_p(d_slots_ptr or None), C.c_void_p(d_moments_ptr),
+                                   C.c_void_p(stream_ptr)), "mrt_moments_device")
+
+
+def moments_se(moments):
+    """Standard error of each pixel's mean luminance from its moments (..., 4): a numpy restatement of
+    include/mrt_adaptive.h's mrt_moments_se in float32 -- +inf below two finite samples."""
+    m = np.asarray(moments, dtype=np.float32)
+    sx, sy, n = m[..., 0], m[..., 1], m[..., 2]
+    with np.errstate(all="ignore"):
+        mean = sx / n
+        var = sy / n - mean * mean
+        var = np.where(var < 0, np.float32(0), var)
+        se = np.sqrt(var / (n - np.float32(1)))
+    return np.where(n < 2, np.float32(np.inf), se).astype(np.float32)
+
+
+def moments_refine(moments, atol, rtol):
+    """The adaptive render's own decision (mrt_moments_decide, the library's mrt_moments_refine) for
+    float32 moments (..., 4): a bool array, True where the pixel refines."""
+    m = np.ascontiguousarray(moments, dtype=np.float32)
+    out = np.zeros(m.shape[:-1], dtype=np.uint8)
+    check(lib().mrt_moments_decide(m.ctypes.data, out.size, atol, rtol, out.ctypes.data, None), "mrt_moments_decide")
+    return out.astype(bool)
 
 
 def tonemap_argb(img):

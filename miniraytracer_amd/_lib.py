@@ -80,6 +80,14 @@ class MrtDenoiseParams(C.Structure):
                 ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class MrtAdaptiveParams(C.Structure):
+    """mrt_adaptive_params (include/mrt.h): refinement passes and the standard-error target atol + rtol * mean."""
+    _fields_ = [("max_passes", C.c_uint32), ("atol", C.c_float), ("rtol", C.c_float)]
+
+
+MOMENTS_DEPTH = 16  # samples mrt_moments_kernel keeps in flight (mrt_adaptive.hip MRT_MOMENTS_DEPTH): its loop's threshold
+
+
 class MrtError(RuntimeError):
     pass
 
@@ -175,6 +183,17 @@ def lib():
     L.mrt_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(MrtDenoiseParams),
                                      C.c_void_p, C.c_void_p, C.c_void_p]
     L.mrt_denoise_device.restype = st
+    L.mrt_moments.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.mrt_moments.restype = st
+    L.mrt_moments_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mrt_moments_device.restype = st
+    L.mrt_moments_decide.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    L.mrt_moments_decide.restype = st
+    L.mrt_default_adaptive_params.argtypes = [C.POINTER(MrtAdaptiveParams)]
+    L.mrt_default_adaptive_params.restype = None
+    L.mrt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(MrtRenderDesc), C.POINTER(MrtAdaptiveParams), C.c_void_p, C.c_void_p,
+                                      C.POINTER(C.c_uint64), C.c_void_p]
+    L.mrt_render_adaptive.restype = st
     _lib = L
     return L
 
@@ -196,4 +215,5 @@ EXPORTS = [
     "mrt_abi_version", "mrt_comm_unique_id", "mrt_comm_init_rank", "mrt_comm_init_all", "mrt_comm_free",
     "mrt_gather_shard_pixels", "mrt_gather_frame", "mrt_render_gather",
     "mrt_render_aux", "mrt_render_aux_device", "mrt_default_denoise_params", "mrt_denoise", "mrt_denoise_device",
+    "mrt_moments", "mrt_moments_device", "mrt_moments_decide", "mrt_default_adaptive_params", "mrt_render_adaptive",
 ]

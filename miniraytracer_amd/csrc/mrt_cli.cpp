@@ -18,6 +18,12 @@
 // PREFIX_normal.pfm and PREFIX_albedo.pfm; -denoise N filters the image with N a-trous passes over
 // those buffers (mrt_denoise, the library's default widths) before -o writes it.  Both work with
 // every backend and -gpus count: each rank fills its own pixels of the shared host buffers.
+// -adaptive N renders adaptively (mrt_render_adaptive): -samples is the base pass, then up to N (1 to
+// 4) refinement passes over the pixels whose standard error misses -atol X + -rtol Y * mean (the
+// library's defaults where not given); -samplemap FILE.pfm writes the samples spent per pixel, grey.
+// A line after "Trace:" reports the mean samples per pixel and the pixels refined per pass.  It
+// composes with -denoise, -aux, -backend cpu and -gpus N over the host assembly (every decision is
+// per pixel, so each rank refines its own); the RCCL gather does not carry adaptive frames.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -42,7 +48,15 @@ int main(int argc, char** argv) {
     const char* gather = nullptr;
     const char* aux = nullptr;
     int denoise = -1;
+    int adaptive = -1;
+    const char* samplemap = nullptr;
+    mrt_adaptive_params ap;
+    mrt_default_adaptive_params(&ap);
     for (int i = 1; i + 1 < argc; i++) {
+        if (!strcmp(argv[i], "-adaptive")) adaptive = atoi(argv[i + 1]);
+        if (!strcmp(argv[i], "-atol")) ap.atol = strtof(argv[i + 1], nullptr);
+        if (!strcmp(argv[i], "-rtol")) ap.rtol = strtof(argv[i + 1], nullptr);
+        if (!strcmp(argv[i], "-samplemap")) samplemap = argv[i + 1];
         if (!strcmp(argv[i], "-o")) out = argv[i + 1];
         if (!strcmp(argv[i], "-gather")) gather = argv[i + 1];
         if (!strcmp(argv[i], "-aux")) aux = argv[i + 1];
@@ -52,6 +66,30 @@ int main(int argc, char** argv) {
         fprintf(stderr, "-denoise: 0 to 16 passes\n");
         return 1;
     }
+    bool have_adaptive = false;
+    for (int i = 1; i < argc; i++) have_adaptive |= !strcmp(argv[i], "-adaptive");
+    if (have_adaptive && (adaptive < 1 || adaptive > 4)) {
+        fprintf(stderr, "-adaptive: 1 to 4 refinement passes\n");
+        return 1;
+    }
+    if (!have_adaptive && samplemap) {
+        fprintf(stderr, "-samplemap: needs -adaptive N\n");
+        return 1;
+    }
+    if (have_adaptive && gather && !strcmp(gather, "rccl")) {
+        fprintf(stderr, "-adaptive: the RCCL gather does not carry adaptive frames (use -gather host, the default with -adaptive)\n");
+        return 1;
+    }
+    if (have_adaptive) {  // draw()'s per-pixel mean (mode 0) is what the passes merge: the default unless -mode asks for 1
+        bool have_mode = false;
+        for (int i = 1; i < argc; i++) have_mode |= !strcmp(argv[i], "-mode");
+        if (have_mode && p.threading_mode != 0) {
+            fprintf(stderr, "-adaptive: renders with draw() semantics only (-mode 0)\n");
+            return 1;
+        }
+        p.threading_mode = 0;
+    }
+    ap.max_passes = have_adaptive ? (uint32_t)adaptive : 0u;
     if (gather && strcmp(gather, "rccl") && strcmp(gather, "host")) {
         fprintf(stderr, "-gather: rccl or host\n");
         return 1;
@@ -99,7 +137,7 @@ int main(int argc, char** argv) {
         descs[0].threads = n;
     }
     // the RCCL gather needs a GPU per rank (RCCL refuses two ranks on one device)
-    const bool use_rccl = !cpu && world <= ndev && (gather ? !strcmp(gather, "rccl") : world > 1);
+    const bool use_rccl = !have_adaptive && !cpu && world <= ndev && (gather ? !strcmp(gather, "rccl") : world > 1);
     if (gather && !strcmp(gather, "rccl") && !use_rccl) {
         fprintf(stderr, "-gather rccl: needs the GPU backend and a GPU per rank (%d ranks, %d GPUs)\n", world, ndev);
         return 1;
@@ -111,6 +149,7 @@ int main(int argc, char** argv) {
         if ((st = mrt_comm_init_all((uint32_t)world, devs.data(), comms.data()))) return fail("comm_init_all", st);
     }
     std::vector<float> img((size_t)p.buffer_width * p.buffer_height * 4, 0.0f);
+    std::vector<float> mom(have_adaptive ? img.size() : 0, 0.0f);  // -adaptive: the moments frame (w = samples spent)
     std::vector<uint64_t> rays(world, 0);
     std::vector<mrt_status> sts(world, MRT_OK);
 
@@ -118,8 +157,9 @@ int main(int argc, char** argv) {
     std::vector<std::thread> th;
     for (int r = 0; r < world; r++)
         th.emplace_back([&, r] {
-            sts[r] = use_rccl ? mrt_render_gather(scenes[r], comms[r], &descs[r], r == 0 ? img.data() : nullptr, &rays[r])
-                              : mrt_render(scenes[r], &descs[r], img.data(), &rays[r], nullptr);
+            sts[r] = have_adaptive ? mrt_render_adaptive(scenes[r], &descs[r], &ap, img.data(), mom.data(), &rays[r], nullptr)
+                     : use_rccl    ? mrt_render_gather(scenes[r], comms[r], &descs[r], r == 0 ? img.data() : nullptr, &rays[r])
+                                   : mrt_render(scenes[r], &descs[r], img.data(), &rays[r], nullptr);
         });
     for (auto& t : th) t.join();
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -142,6 +182,32 @@ int main(int argc, char** argv) {
     printf("MiniRayTracer - Scene: %.0fms - Trace: %.2fs - %.3f Mrays/s | %.3f us/ray  [%s, %u spp, %s numerics]\n", gen_ms,
            secs, (total * 0.000001) / secs, (secs * 1000000.0) / (double)total, where, descs[0].sqrt_samples * descs[0].sqrt_samples,
            p.numerics ? "fast" : "exact");
+    if (have_adaptive) {
+        // from the moments frame: a pixel refined in pass k has spent more than the passes before it
+        const size_t npx = (size_t)p.buffer_width * p.buffer_height;
+        double spent = 0;
+        for (size_t i = 0; i < npx; i++) spent += mom[i * 4 + 3];
+        printf("adaptive: %.2f spp mean, atol %g rtol %g, refined", spent / (double)npx, ap.atol, ap.rtol);
+        double before = 0;
+        for (int k = 0; k < adaptive; k++) {
+            const double sq = (double)(descs[0].sqrt_samples << k);
+            before += sq * sq;
+            size_t n = 0;
+            for (size_t i = 0; i < npx; i++) n += mom[i * 4 + 3] > before;
+            printf(" %zu", n);
+        }
+        printf(" of %zu pixels\n", npx);
+        if (samplemap) {
+            FILE* f = fopen(samplemap, "wb");
+            if (!f) return fail("open -samplemap output", MRT_ERR_IO);
+            fprintf(f, "PF\n%u %u\n-1.0\n", p.buffer_width, p.buffer_height);
+            for (size_t i = 0; i < npx; i++) {
+                const float g[3] = {mom[i * 4 + 3], mom[i * 4 + 3], mom[i * 4 + 3]};
+                fwrite(g, 4, 3, f);
+            }
+            fclose(f);
+        }
+    }
     printf("rays %llu\n", (unsigned long long)total);
 
     // -aux / -denoise: the first-hit feature buffers at min(spp, 16) samples -- every rank writes its

@@ -10,6 +10,9 @@ uint32_t mrt_cpu_scene_features(const mrt_cpu_scene* c);
 mrt_status mrt_cpu_render(mrt_cpu_scene* c, const mrt_render_desc* d, float* rgb_out, uint64_t* rays_out, const volatile int* cancel);
 // first-hit feature buffers (mrt_render_aux): host W*H*4 each, owned pixels only
 mrt_status mrt_cpu_render_aux(mrt_cpu_scene* c, const mrt_render_desc* d, float* normal_out, float* albedo_out);
+// the adaptive render (mrt_render_adaptive; arguments checked by the caller)
+mrt_status mrt_cpu_render_adaptive(mrt_cpu_scene* c, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out, float* moments_out,
+                                   uint64_t* rays_out, const volatile int* cancel);
 mrt_status mrt_cpu_progress(mrt_cpu_scene* c, float* pct);
 mrt_status mrt_cpu_last_ms(mrt_cpu_scene* c, float* ms, uint32_t* threads);
 mrt_status mrt_cpu_preview(mrt_cpu_scene* c, float* rgb_out, uint32_t* samples_done);

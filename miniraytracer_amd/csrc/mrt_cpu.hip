@@ -41,6 +41,8 @@
 #include "mrt_cpu.h"
 #include "mrt_tables.h"
 #include "mrt_aux.h"
+#include "mrt_moments.h"
+#include "../../include/mrt_adaptive.h"
 
 using namespace mrtd;
 
@@ -74,6 +76,9 @@ struct mrt_cpu_scene {
     // the framebuffer's size, owner list and contents: workers publish a finished work item (a
     // tile's pixels) under it, mrt_preview copies under it
     std::mutex fb_mu;
+    // the adaptive render's moments sink (mrt_cpu_render_adaptive): a W*H float4 frame; while it is
+    // set, render_tiles adds every sample of a pixel to the pixel's moments beside the fold
+    mrt_m4* mom = nullptr;
 };
 
 // the two hot-path instantiations of the host backend: any linear hit program through the
@@ -189,6 +194,8 @@ static void render_tiles(mrt_cpu_scene* c, const mrt_render_desc* d, const std::
             for (uint32_t x = t.xmin; x < t.xmax; x++) {
                 const uint32_t pix = x + y * W;
                 f3 col{0, 0, 0};
+                mrt_m4 mo{0.0f, 0.0f, 0.0f, 0.0f};
+                if (c->mom) mo = c->mom[pix];
                 for (uint32_t s = 0; s < ns; s++) {
                     const uint64_t path_id = (uint64_t)pix * ns + s;
                     PathState ps;
@@ -200,7 +207,9 @@ static void render_tiles(mrt_cpu_scene* c, const mrt_render_desc* d, const std::
                     const f3 L = trace_path<F>(S, ps, d->max_bounces, lev, Ls);
                     my_rays += ps.rays();
                     col = fold_sample(col, L, s, d->mode, d->max_luminance);
+                    if (c->mom) mo = mrt_moments_add(mo, L.x, L.y, L.z);
                 }
+                if (c->mom) c->mom[pix] = mo;
                 col = final_pixel(col, ns, d->mode, d->max_luminance);
                 float* o = tb.data() + ((size_t)(x - t.xmin) + (size_t)(y - t.ymin) * tw) * 4;
                 o[0] = col.x;
@@ -363,6 +372,64 @@ mrt_status mrt_cpu_render(mrt_cpu_scene* c, const mrt_render_desc* d, float* rgb
     c->last_threads = n;
     if (rays_out) *rays_out = rays.load();
     if (cancelled.load()) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled (partial image)");
+    return MRT_OK;
+}
+
+// The adaptive render (include/mrt.h mrt_render_adaptive) on the CPU backend: the passes are
+// mrt_cpu_render calls with the moments sink set -- pass 0 the desc as it stands, pass k the refined
+// pixels as a pixel list -- and the merge is include/mrt_adaptive.h's, per listed pixel.
+mrt_render_desc mrt_internal_adaptive_pass(const mrt_render_desc* d, uint32_t k, const uint32_t* pixels, uint32_t n_pixels) {
+    mrt_render_desc dk = *d;
+    dk.sqrt_samples = d->sqrt_samples << k;
+    dk.seed = splitmix64(d->seed + k);
+    dk.pixels = pixels;
+    dk.n_pixels = n_pixels;
+    return dk;
+}
+
+mrt_status mrt_cpu_render_adaptive(mrt_cpu_scene* c, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out, float* moments_out,
+                                   uint64_t* rays_out, const volatile int* cancel) {
+    if (d->flags & MRT_RF_FAST) return mrt_internal_fail(MRT_ERR_INVALID, "the CPU backend implements the exact numerics contract only");
+    const size_t npx = (size_t)d->width * d->height;
+    const std::vector<uint32_t> px0 = mrt_internal_local_pixels(d);
+    std::vector<float> mom_own, pass_rgb;
+    if (!moments_out) {
+        mom_own.assign(npx * 4, 0.0f);
+        moments_out = mom_own.data();
+    }
+    for (uint32_t q : px0) memset(moments_out + (size_t)q * 4, 0, 16);
+    struct Sink {  // (unset on every way out)
+        mrt_cpu_scene* c;
+        ~Sink() { c->mom = nullptr; }
+    } sink{c};
+    c->mom = (mrt_m4*)moments_out;
+    uint64_t total = 0, rays = 0;
+    mrt_status st = mrt_cpu_render(c, d, rgb_out, &rays, cancel);
+    total += rays;
+    if (rays_out) *rays_out = total;
+    if (st) return st;
+    float N = (float)(d->sqrt_samples * d->sqrt_samples);
+    std::vector<float> lm(px0.size() * 4);
+    std::vector<uint32_t> list;
+    for (uint32_t k = 1; k <= p->max_passes; k++) {
+        if (cancel && *cancel) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled (between passes)");
+        for (size_t i = 0; i < px0.size(); i++) memcpy(&lm[i * 4], moments_out + (size_t)px0[i] * 4, 16);
+        const std::vector<uint32_t> slots = mrt_internal_refine_slots(lm.data(), (uint32_t)px0.size(), p->atol, p->rtol);
+        if (slots.empty()) break;
+        list.resize(slots.size());
+        for (size_t j = 0; j < slots.size(); j++) list[j] = px0[slots[j]];
+        const mrt_render_desc dk = mrt_internal_adaptive_pass(d, k, list.data(), (uint32_t)list.size());
+        if (pass_rgb.empty()) pass_rgb.assign(npx * 4, 0.0f);
+        rays = 0;
+        st = mrt_cpu_render(c, &dk, pass_rgb.data(), &rays, cancel);
+        total += rays;
+        if (rays_out) *rays_out = total;
+        if (st) return st;
+        const float nsf = (float)(dk.sqrt_samples * dk.sqrt_samples);
+        for (uint32_t q : list)
+            for (int ch = 0; ch < 3; ch++) rgb_out[(size_t)q * 4 + ch] = mrt_adaptive_merge(rgb_out[(size_t)q * 4 + ch], pass_rgb[(size_t)q * 4 + ch], N, nsf);
+        N = N + nsf;
+    }
     return MRT_OK;
 }
 

@@ -26,6 +26,7 @@
 #include "mrt_aux.h"
 #include "mrt_tables.h"
 #include "mrt_cpu.h"
+#include "mrt_moments.h"
 #include "../../include/mrt_tonemap.h"
 
 using namespace mrtd;
@@ -421,6 +422,14 @@ struct mrt_scene {
     uint64_t last_paths = 0;
     uint32_t last_numerics = 0;
     uint32_t prog_ops = 0;  // linear hit program length (0: generic machine)
+    // the adaptive render's moments sink (internal, mrt_render_adaptive): while mom is set, every
+    // launch chunk's radiance is also added to mom[mom_slots ? mom_slots[lp] : lp] (mrt_moments_kernel)
+    // on the render's stream, after the chunk's fold and before the next launch reuses the buffer
+    float* mom = nullptr;
+    const uint32_t* mom_slots = nullptr;
+    // its refinement passes' pixel lists come from mrt_internal_refine_slots over checked pixels (in
+    // range, no repeats): mrt_prepare skips the list check (a sort) for them
+    bool trust_pixels = false;
 };
 
 // LDS words per lane of a launch's walk stacks: the generic machine's frames (two words each) and
@@ -699,7 +708,7 @@ extern "C" mrt_status mrt_prepare(mrt_scene* s, const mrt_render_desc* d) {
     if (d->flags & MRT_RF_REF_ORDER)
         return mrt_internal_fail(MRT_ERR_INVALID, "MRT_RF_REF_ORDER is a CPU-backend mode (the GPU keys its PCG streams per path)");
     mrt_status st;
-    if ((st = mrt_internal_check_pixels(d))) return st;
+    if (!s->trust_pixels && (st = mrt_internal_check_pixels(d))) return st;
     HIPCHK(hipSetDevice(s->device));
     bool relayout = !s->have_ws || !same_layout(s->wdesc, s->wpixels, *d);
     uint32_t ns = d->sqrt_samples * d->sqrt_samples;
@@ -984,6 +993,7 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
             hipLaunchKernelGGL(mrt_fold_kernel, dim3((nthr + 255) / 256), dim3(256), 0, q, d_rad, s->d_acc.p, s->npix, s0, s1, d->mode,
                                d->max_luminance, fe);
         HIPCHK(hipGetLastError());
+        if (s->mom && (st = mrt_internal_moments_enqueue(d_rad, s->npix, s1 - s0, s->mom_slots, s->mom, q))) return st;
         if (preview) {  // the image after s1 samples, copied under the sequence lock
             hipLaunchKernelGGL(mrt_final_kernel, dim3((s->npix + MRT_FINAL_WG - 1) / MRT_FINAL_WG), dim3(MRT_FINAL_WG), 0, q, s->d_acc.p, s->d_prev.p,
                                s->npix, s1, d->mode, d->max_luminance,
@@ -1010,9 +1020,11 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
     return MRT_OK;
 }
 
-extern "C" mrt_status mrt_render(mrt_scene* s, const mrt_render_desc* d, float* rgb_out, uint64_t* rays_out, const volatile int* cancel) {
-    if (!s || !d || !rgb_out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_render: null");
-    if (s->cpu) return mrt_cpu_render(s->cpu, d, rgb_out, rays_out, cancel);
+// mrt_render on the GPU up to the end of the wait: the render of d into the scene's device
+// framebuffer (d_out, local-pixel order; s->npix pixels) and its ray total (d_rays), both complete
+// when it returns.  *cancelled: the caller's flag stopped it (a partial image).
+static mrt_status render_wait(mrt_scene* s, const mrt_render_desc* d, const volatile int* cancel, bool* was_cancelled) {
+    *was_cancelled = false;
     s->n_chunks.store(0, std::memory_order_release);
     if (cancel && *cancel) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled");
     mrt_render_desc dc = *d;  // a cancellable render runs as >= 16 launches; cancel lands between them
@@ -1045,6 +1057,15 @@ extern "C" mrt_status mrt_render(mrt_scene* s, const mrt_render_desc* d, float* 
     }
     s->ev_done_pending = false;
     if (cancelled) HIPCHK(hipMemset(s->d_counter + 4, 0, 8));  // the render is over: clear the flag for the next one
+    *was_cancelled = cancelled;
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_render(mrt_scene* s, const mrt_render_desc* d, float* rgb_out, uint64_t* rays_out, const volatile int* cancel) {
+    if (!s || !d || !rgb_out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_render: null");
+    if (s->cpu) return mrt_cpu_render(s->cpu, d, rgb_out, rays_out, cancel);
+    bool cancelled = false;
+    if (mrt_status st = render_wait(s, d, cancel, &cancelled)) return st;
     std::vector<float> local((size_t)s->npix * 4);
     std::vector<uint32_t> px = mrt_internal_local_pixels(d);
     HIPCHK(hipMemcpy(local.data(), s->d_out.p, local.size() * 4, hipMemcpyDeviceToHost));
@@ -1054,6 +1075,91 @@ extern "C" mrt_status mrt_render(mrt_scene* s, const mrt_render_desc* d, float* 
     if (rays_out) *rays_out = rays;
     if (cancelled) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled (partial image)");
     return MRT_OK;
+}
+
+// ---- the adaptive render (include/mrt.h "sample moments and the adaptive render") ----
+// The call's own device buffers: the running colour C and the moments m of the pass-0 local pixels
+// (one slot each) and the slot map of the current refinement pass.  Every pass is a render_wait --
+// mrt_render's own path, stream-ordered fold included -- with the moments sink set; a refinement
+// pass lands in the scene's d_out in list order and mrt_merge_kernel folds it into C through the
+// slot map.  The decision runs on the host from a copy of the moments.
+namespace {
+struct AdaptiveBufs {  // one allocation: C, then m (n float4 each), then the slot map
+    float *C = nullptr, *m = nullptr;
+    uint32_t* slots = nullptr;
+    mrt_scene* s = nullptr;
+    ~AdaptiveBufs() {
+        if (s) s->mom = nullptr, s->mom_slots = nullptr, s->trust_pixels = false;
+        if (C) (void)hipFree(C);
+    }
+};
+}  // namespace
+
+static mrt_status render_adaptive_gpu(mrt_scene* s, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out, float* moments_out,
+                                      uint64_t* rays_out, const volatile int* cancel) {
+    HIPCHK(hipSetDevice(s->device));
+    const std::vector<uint32_t> px0 = mrt_internal_local_pixels(d);
+    const uint32_t n0 = (uint32_t)px0.size();
+    AdaptiveBufs B;
+    if (hipMalloc((void**)&B.C, (size_t)n0 * 36 + 16) != hipSuccess) return mrt_internal_fail(MRT_ERR_OOM, "mrt_render_adaptive: device buffers");
+    B.m = B.C + (size_t)n0 * 4;
+    B.slots = (uint32_t*)(B.m + (size_t)n0 * 4);
+    HIPCHK(hipMemset(B.m, 0, (size_t)n0 * 16));
+    B.s = s;  // (from here on the sink is unset on every way out)
+    uint64_t total = 0;
+    if (rays_out) *rays_out = 0;
+    // one pass: the render with the sink set; its pixels are then in d_out, its rays added to the total
+    auto pass = [&](const mrt_render_desc* dk, const uint32_t* d_slots) -> mrt_status {
+        s->mom = B.m;
+        s->mom_slots = d_slots;
+        s->trust_pixels = d_slots != nullptr;  // a refinement pass: the list is this call's own
+        bool cancelled = false;
+        const mrt_status st = render_wait(s, dk, cancel, &cancelled);
+        s->mom = nullptr;
+        s->mom_slots = nullptr;
+        s->trust_pixels = false;
+        if (st) return st;
+        uint64_t rays = 0;
+        HIPCHK(hipMemcpy(&rays, s->d_rays, 8, hipMemcpyDeviceToHost));
+        total += rays;
+        if (rays_out) *rays_out = total;
+        if (cancelled) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled (partial image)");
+        return MRT_OK;
+    };
+    mrt_status st = pass(d, nullptr);
+    if (st) return st;
+    HIPCHK(hipMemcpy(B.C, s->d_out.p, (size_t)n0 * 16, hipMemcpyDeviceToDevice));
+    float N = (float)(d->sqrt_samples * d->sqrt_samples);
+    std::vector<float> hm((size_t)n0 * 4);
+    std::vector<uint32_t> list;
+    for (uint32_t k = 1; k <= p->max_passes; k++) {
+        if (cancel && *cancel) return mrt_internal_fail(MRT_ERR_CANCELLED, "cancelled (between passes)");
+        HIPCHK(hipMemcpy(hm.data(), B.m, hm.size() * 4, hipMemcpyDeviceToHost));
+        const std::vector<uint32_t> slots = mrt_internal_refine_slots(hm.data(), n0, p->atol, p->rtol);
+        if (slots.empty()) break;
+        list.resize(slots.size());
+        for (size_t j = 0; j < slots.size(); j++) list[j] = px0[slots[j]];
+        HIPCHK(hipMemcpy(B.slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice));
+        const mrt_render_desc dk = mrt_internal_adaptive_pass(d, k, list.data(), (uint32_t)list.size());
+        if ((st = pass(&dk, B.slots))) return st;
+        const float nsf = (float)(dk.sqrt_samples * dk.sqrt_samples);
+        if ((st = mrt_internal_merge_enqueue((const float*)s->d_out.p, (uint32_t)slots.size(), B.slots, B.C, N, nsf, nullptr))) return st;
+        HIPCHK(hipStreamSynchronize(nullptr));  // (the next pass may regrow d_out; the slot map is rewritten)
+        N = N + nsf;
+    }
+    std::vector<float> local((size_t)n0 * (moments_out ? 8 : 4));  // C, then m: one copy
+    HIPCHK(hipMemcpy(local.data(), B.C, local.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < px0.size(); i++) memcpy(rgb_out + (size_t)px0[i] * 4, &local[i * 4], 16);
+    if (moments_out)
+        for (size_t i = 0; i < px0.size(); i++) memcpy(moments_out + (size_t)px0[i] * 4, &local[((size_t)n0 + i) * 4], 16);
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_render_adaptive(mrt_scene* s, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out,
+                                          float* moments_out, uint64_t* rays_out, const volatile int* cancel) {
+    if (mrt_status st = mrt_internal_adaptive_check(s, d, p, rgb_out)) return st;
+    if (s->cpu) return mrt_cpu_render_adaptive(s->cpu, d, p, rgb_out, moments_out, rays_out, cancel);
+    return render_adaptive_gpu(s, d, p, rgb_out, moments_out, rays_out, cancel);
 }
 
 // ---- first-hit feature buffers (include/mrt.h "feature buffers and denoise") ----
