@@ -20,12 +20,11 @@ MRT_DFN AuxSum aux_zero() { return AuxSum{{0.0f, 0.0f, 0.0f}, 0.0f, {0.0f, 0.0f,
 // position -- added to the pixel's sums.
 template <uint32_t F>
 MRT_DFN void aux_first_hit(const DScene& S, PathState& ps, const LStack& Ls, AuxSum& a) {
+    static_assert(!kBox6Walk<F>, "exact contract: no Cornell fast walk (its hit table is the path loop's)");
     PhaseClock ph{};
     HitRec rec;
     bool hit;
-    if constexpr (kBox6Walk<F>)
-        hit = scene_hit_sig<F>(S, ps.r, kCornellTmin, rec, Ls, cornell_light_t<F>(const_ptr(S.prog), ps.r), cornell_sphere_inv_rad(const_ptr(S.prog)));
-    else if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, ps.r, 0.001f, rec, Ls);
+    if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, ps.r, 0.001f, rec, Ls);
     else if constexpr ((F & FT_LIN) != 0) hit = scene_hit_lin<F>(S, ps.r, 0.001f, rec, Ls, ps.rng, ph);
     else hit = scene_hit<F>(S, ps.r, 0.001f, rec, ps.rng, Ls);
     f3 alb{0.0f, 0.0f, 0.0f};

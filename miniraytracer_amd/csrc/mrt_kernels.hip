@@ -244,8 +244,11 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     // per wave: its stacks and queues ([slot][word][lane])
-    const uint32_t words = (P.lds_frames * 2 + P.lds_rays * 11 + P.lds_mesh + P.lds_save + LK * 4 + PathQ<F>::words) * 64;
-    uint32_t* wb = lds + wave * words;
+    // (a kBox6Walk kernel's slice starts with the wave's copy of the Cornell hit table, mrt_sig.h: in a
+    // one-wave group at LDS address 0, a constant)
+    constexpr uint32_t hit_words = kBox6Walk<F> ? kHitLdsBytes / 4u : 0u;
+    const uint32_t words = (P.lds_frames * 2 + P.lds_rays * 11 + P.lds_mesh + P.lds_save + LK * 4 + PathQ<F>::words) * 64 + hit_words;
+    uint32_t* wb = lds + wave * words + hit_words;
     uint32_t* const wmesh = wb + P.lds_frames * 128 + P.lds_rays * 704;
     float4* tree = nullptr;
     if constexpr (TreeOf<F>::on) {
@@ -256,7 +259,10 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
         __syncthreads();
     }
     const LStack Ls{wb, (float*)(wb + P.lds_frames * 128), wmesh, (float*)(wmesh + P.lds_mesh * 64), lane, tree,
-                    TreeOf<F>::on ? P.tree_n : 0u};
+                    TreeOf<F>::on ? P.tree_n : 0u,
+                    !kBox6Walk<F> ? 0u
+                    : TreeOf<F>::wg == 64u ? (uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)lds  // (one wave: its slice is the group's)
+                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(wb - hit_words))};
     // the wave's queue of path starts ([word][entry], PathQ): after the fold levels
     float* const Lq = (float*)(wmesh + (P.lds_mesh + P.lds_save + LK * 4) * 64);
     const DScene& S = P.sc;
@@ -461,6 +467,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
 #endif
     constexpr bool kShared = (F & FT_MESH) == 0 && (MRT_SHARED_WIDE || !PathOcc<F>::kWide);
     constexpr bool kResume = MRT_SIG_OF(F) == SIG_ROOM_MESH;
+    static_assert(kShared || !kBox6Walk<F>, "the Cornell fast walk's hit table is set up by the shared-constructor loop");
     if constexpr (kShared) {
         // One iteration: (1) every lane with a ray traces one segment; a path that ends is folded
         // and stored; (2) lanes without a path take new ones (camera ray arguments); (3) ONE
@@ -479,7 +486,18 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
         bool st_pend = false;
         // Cornell fast walk: the sphere's 1 / radius, once per launch (mrt_sig.h cornell_sphere_inv_rad)
         float sph_inv_rad = 0.0f;
-        if constexpr (kBox6Walk<F>) sph_inv_rad = cornell_sphere_inv_rad(const_ptr(S.prog));
+        if constexpr (kBox6Walk<F>) {
+            sph_inv_rad = cornell_sphere_inv_rad(const_ptr(S.prog));
+            // the scene's hit table (kHitCount entries behind the program's END op, mrt_tables.hip
+            // cornell_hit_fill) into the wave's LDS: the first three 16-byte quads of each entry, one
+            // per lane, packed (entry e's quad q lands at quad 3 e + q = the lane).  Only this wave
+            // reads them, after this store in its own LDS queue: no barrier.
+            const uint32_t e = lane / 3u, qd = lane - e * 3u;
+            if (lane < kHitCount * (kHitLdsWords / 4u)) {
+                const v4f* src = reinterpret_cast<const v4f*>(S.prog + kSigs[SIG_CORNELL].n) + e * (kHitWords / 4u) + qd;
+                ((MRT_LDS_AS v4f*)(uintptr_t)Ls.hits)[lane] = *src;
+            }
+        }
         for (;;) {
             bool want_ray = false;
             // the next ray's arguments: written and read within one iteration (declared here, a

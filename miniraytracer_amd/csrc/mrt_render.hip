@@ -519,7 +519,14 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
     UP((const float4*)v->perlin_ranvec, 256, &S.ranvec);
     UP(v->perlin_perm, 768, &S.perm);
     UP(v->texels, (size_t)v->n_texels, &S.texels);
-    UP(T.prog.data(), T.prog.size(), &S.prog);
+    if (T.cornell_hits.empty()) {
+        UP(T.prog.data(), T.prog.size(), &S.prog);
+    } else {  // Cornell shape: the hit table behind the END op, one op's size per entry (mrt_sig.h)
+        std::vector<LinOp> pw(T.prog);
+        pw.resize(T.prog.size() + kHitCount);
+        memcpy(pw.data() + T.prog.size(), T.cornell_hits.data(), (size_t)kHitCount * kHitWords * 4);
+        UP(pw.data(), pw.size(), &S.prog);
+    }
     {
         const char* e = getenv("MRT_NO_REWRITE");  // A/B hook: the interpreter on the program as compiled
         if (!T.prog_fast.empty() && !(e && *e && *e != '0')) UP(T.prog_fast.data(), T.prog_fast.size(), &s->prog_fast);
@@ -588,6 +595,11 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
         const int nb_vgpr = std::max(1, std::min(8, 512 / vg) * 4 / (int)waves_per_wg);  // waves per CU / waves per group
         auto groups = [&](size_t lds) { return std::max(1, lds ? std::min<int>(nb_vgpr, (int)((160u * 1024u) / lds)) : nb_vgpr); };
         L.lds_bytes = (size_t)waves_per_wg * 64 * 4 * (lds_stack_words(s, L.lds_save) + tabs[k]->lev_k[s->variant] * 4 + tabs[k]->pq[s->variant]);
+        // + each wave's copy of the Cornell hit table (mrt_sig.h; T.cornell_hits, uploaded behind the program)
+        if (tabs[k]->box6_walk[s->variant]) {
+            if (T.cornell_hits.empty()) return mrt_internal_fail(MRT_ERR_INVALID, "Cornell walk without a hit table");
+            L.lds_bytes += (size_t)waves_per_wg * kHitLdsBytes;
+        }
         if (L.lds_bytes > (size_t)prop.sharedMemPerBlock) return mrt_internal_fail(MRT_ERR_INVALID, "scene graph too deep for the LDS stacks");
         int nb = groups(L.lds_bytes);
         if (tabs[k]->tree[s->variant]) {

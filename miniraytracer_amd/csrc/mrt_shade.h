@@ -184,6 +184,23 @@ MRT_DFN f3 leaf_pdf_generate(const DScene& S, const mrt_node& n, f3 origin, floa
 }
 template <uint32_t F>
 MRT_DFN f3 biased_pdf_generate(const DScene& S, f3 origin, float time, Pcg& rng, Draws& dr) {
+    if constexpr (kBox6Walk<F>) {
+        // the one biased leaf is op 3's rect bit for bit (DScene::light_once): xz_rect::pdf_generate
+        // from the program's words, one batch of scalar loads at a constant offset -- the leaf's kind
+        // word and then, after a wait, its bounds were two dependent round trips
+        if (S.light_once) {
+            if (S.blist) (void)dr.next(rng);  // object_list::pdf_generate's index draw (scene_object.h:72-77)
+            const CornellRect d = cornell_load(const_ptr(S.prog)[3]);
+            mrt_node n;
+            n.kind = MRT_K_XZ;
+            n.f[0] = __uint_as_float(d.b0);
+            n.f[1] = __uint_as_float(d.b1);
+            n.f[2] = __uint_as_float(d.b2);
+            n.f[3] = __uint_as_float(d.b3);
+            n.f[4] = __uint_as_float(d.k);
+            return leaf_pdf_generate<F>(S, n, origin, time, rng, dr);
+        }
+    }
     if (!S.blist) {
         const mrt_node n = ld_node(const_ptr(S.bleaf));
         return leaf_pdf_generate<F>(S, n, origin, time, rng, dr);
@@ -507,11 +524,12 @@ MRT_DFN bool shade_hit(const DScene& S, PathState& ps, uint32_t max_bounces, con
 template <uint32_t F, uint32_t LK>
 MRT_DFN bool trace_segment(const DScene& S, PathState& ps, uint32_t max_bounces, const LevStore<LK>& lev,
                                               const LStack& Ls, f3* L, PhaseClock& ph, const CritSink& cs = CritSink{0u, 0u}) {
+    // (the Cornell fast walk runs in the path loop's shared-constructor form only -- trace_split --,
+    // which sets up the wave's hit table)
+    static_assert(!kBox6Walk<F>, "the Cornell fast walk is trace_split's");
     HitRec rec;
     bool hit;
-    if constexpr (kBox6Walk<F>)
-        hit = scene_hit_sig<F>(S, ps.r, kCornellTmin, rec, Ls, cornell_light_t<F>(const_ptr(S.prog), ps.r), cornell_sphere_inv_rad(const_ptr(S.prog)));
-    else if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, ps.r, 0.001f, rec, Ls);
+    if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, ps.r, 0.001f, rec, Ls);
     else if constexpr ((F & FT_LIN) != 0) hit = scene_hit_lin<F>(S, ps.r, 0.001f, rec, Ls, ps.rng, ph);
     else hit = scene_hit<F>(S, ps.r, 0.001f, rec, ps.rng, Ls);
     PH_MARK(ph, 1);
@@ -579,7 +597,8 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     HitRec rec;
     Ray& r = ps.r;
     bool hit;
-    if constexpr (kBox6Walk<F>) hit = scene_hit_sig<F>(S, r, kCornellTmin, rec, Ls, ps.lt, inv_rad);  // (ps.lt: set where the path loop makes r)
+    DMat M;  // the hit's material: the Cornell fast walk reads it from its hit table, with the record
+    if constexpr (kBox6Walk<F>) hit = scene_hit_sig<F>(S, r, kCornellTmin, rec, Ls, ps.lt, inv_rad, &M);  // (ps.lt: set where the path loop makes r)
     else if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, r, 0.001f, rec, Ls);
     else if constexpr ((F & FT_LIN) != 0) hit = scene_hit_lin<F>(S, r, 0.001f, rec, Ls, ps.rng, ph);
     else hit = scene_hit<F>(S, r, 0.001f, rec, ps.rng, Ls);
@@ -598,7 +617,7 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
         }
         return true;
     }
-    const DMat M = S.mats[rec.mat];
+    if constexpr (!kBox6Walk<F>) M = S.mats[rec.mat];
     if (M.kind == MRT_M_LIGHT) {  // diffuse_light: sampleEmissive, never scatters (material.h:190-199)
         BSTAT(2);
         *L = dot(rec.n, r.d) < 0.0f ? fmul(M.p, mat_color<F>(S, M, rec)) : f3{0, 0, 0};

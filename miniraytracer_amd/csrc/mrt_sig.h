@@ -426,9 +426,8 @@ struct SigWalk {
 
 // Tolerance contract, Cornell box shape (scene 5, scene.cpp:286-330) whose box is box.h's six rects
 // (MRT_F_BOX6 on op 8): the walk written out for the ops the shape fixes, with the closest hit's
-// record carried per lane through the walk (a code, a plane, a sign, a material: a few selects per
-// primitive) instead of derived afterwards from the winning op (per-lane node loads and a switch on
-// its kind) -- no branch, no LDS.
+// identity carried per lane through the walk (one select per primitive) instead of its record
+// derived afterwards from the winning op (per-lane node loads and a switch on its kind).
 //   * the root list's and the instance's bounding boxes are not tested: every primitive test below
 //     is exact geometry, a box test only skips work (object_list::hit, scene_object.h:83;
 //     rotate_y::hit, scene_object.cpp:72);
@@ -438,17 +437,39 @@ struct SigWalk {
 //     face's outward normal rotated back (scene_object.cpp:85-93).  Differs from the reference's
 //     per-face tests and frame round trip by rounding only.
 // Walls and sphere are lin_prim_t's tests in op order (ties to the later op, as closest narrowing).
+//
+// The walk carries the closest hit's distance and its IDENTITY only: the shape has 14 of them (six
+// room faces, the light, six box faces, the sphere), and everything else the record and the shading
+// read of a hit -- the world-space normal (a box face's rotated back: the rotation is a constant of
+// the scene), the plane the point is put on, the code of the record's branches, the material's
+// words -- is a constant of the uploaded scene.  The host writes it as a table behind the program's
+// END op (mrt_tables.hip cornell_hit_fill), each wave copies the table into its LDS once, and the
+// record is one lookup by identity after the walk -- instead of per-lane selects of wave-uniform
+// words (a v_mov from the SGPR + a v_cndmask each) in every one of the four tests, a normal built
+// and rotated per ray, and a dependent global load of the material.
 #ifndef MRT_CORNELL_BATCHES
 #define MRT_CORNELL_BATCHES 2
 #endif
+// hit identities: room face 2 * axis + side (side 1: the max plane), the light (op 3), box face
+// kHitBox + 2 * axis + (the ray goes up the axis: the min plane, outward normal -1), the sphere
+enum : uint32_t { kHitRoom = 0, kHitLight = 6, kHitBox = 7, kHitSphere = 13, kHitCount = 14, kHitNone = kHitCount };
+// A table entry in memory, one LinOp's size: words 0-2 the normal (unused for the sphere), 3 the plane
+// (a box face's in the box frame), 4 the code -- 1-3 world rect of axis code-1, 4-6 box face of axis
+// code-4, 7 sphere --, 5-7 the DMat's kind, p, flags, 8-11 its col; 12-15 zero.  In LDS the first 12
+// words of each entry, entries 12 words apart: a ds_read_b128 serves 16 lanes per LDS cycle and word
+// w lies in bank w mod 64, so the 14 entries' quads start at banks 12 i mod 64 = 0, 12, 24, 36, 48,
+// 60, 8, 20, 32, 44, 56, 4, 16, 28 -- four banks each, no two overlapping: any mix of identities in
+// a wave reads without a bank conflict (16 words apart, entries i and i + 4 share their banks).
+static constexpr uint32_t kHitWords = 16, kHitLdsWords = 12;
+static constexpr uint32_t kHitLdsBytes = kHitCount * kHitLdsWords * 4;  // 672 per wave
+static_assert(sizeof(LinOp) == kHitWords * 4 && kHitLdsBytes % 16 == 0, "hit table entries are uploaded as trailing ops");
 struct CornellRec {
-    float closest, k, ns;
-    uint32_t code, mat;  // code: 0 none; 1-3 world rect of axis code-1 (plane k); 4-6 box face of axis code-4; 7 sphere
+    float closest;
+    uint32_t id;    // cornell_fast_hit: the hit's identity (kHitNone: none)
+    float ns;       // room_walls_op only (cornell_room<.., false>): the face's normal sign,
+    uint32_t code;  //   and 0 none / 1 + the face's axis
 };
-// A rect op's words (its LinOp's mat and f[0..5]) loaded into SGPRs.  The walk loads all six rects'
-// words as one batch and takes them at one point (the asms, issued back to back after the loads): one
-// scalar-cache round trip for the walls -- the compiler otherwise loaded each op's fields in two
-// dependent rounds, the material lazily inside a branch on the hit (12 round trips for the walls).
+// A rect op's words (its LinOp's mat and f[0..5]) loaded into SGPRs (the light's: cornell_light_t)
 struct CornellRect {
     uint32_t mat, b0, b1, b2, b3, k, ns;
 };
@@ -456,33 +477,29 @@ MRT_DFN CornellRect cornell_load(const MRT_CONST_AS LinOp& o) {
     const MRT_CONST_AS uint32_t* q = reinterpret_cast<const MRT_CONST_AS uint32_t*>(&o);
     return CornellRect{q[3], q[4], q[5], q[6], q[7], q[8], q[9]};
 }
-MRT_DFN void cornell_take1(CornellRect& d) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+s"(d.mat), "+s"(d.b0), "+s"(d.b1), "+s"(d.b2), "+s"(d.b3), "+s"(d.k), "+s"(d.ns));
-#else
-    (void)d;
-#endif
-}
+// The words of the walk's ops are loaded as batches of scalar loads and taken at one point (the
+// asms, issued back to back after the loads): one scalar-cache round trip per batch -- the compiler
+// otherwise loaded an op's fields in dependent rounds.
 // translate(rotate_y(box)): rotate_y's (sin, cos), translate's offset (op 7), the box's planes
-// and material (op 8); the sphere's centre, radius and material (op 17)
+// (op 8); the sphere's centre and radius (op 17)
 struct CornellBox {
-    uint32_t s, c, o0, o1, o2, lo0, lo1, lo2, hi0, hi1, hi2, mat;
+    uint32_t s, c, o0, o1, o2, lo0, lo1, lo2, hi0, hi1, hi2;
 };
 struct CornellSphere {
-    uint32_t c0, c1, c2, rad, mat;
+    uint32_t c0, c1, c2, rad;
 };
 MRT_DFN CornellBox cornell_load_box(const MRT_CONST_AS LinOp& io, const MRT_CONST_AS LinOp& bo) {
     const MRT_CONST_AS uint32_t* qi = reinterpret_cast<const MRT_CONST_AS uint32_t*>(&io);
     const MRT_CONST_AS uint32_t* qb = reinterpret_cast<const MRT_CONST_AS uint32_t*>(&bo);
-    return CornellBox{qi[10], qi[11], qi[12], qi[13], qi[14], qb[10], qb[11], qb[12], qb[13], qb[14], qb[15], qb[3]};
+    return CornellBox{qi[10], qi[11], qi[12], qi[13], qi[14], qb[10], qb[11], qb[12], qb[13], qb[14], qb[15]};
 }
 MRT_DFN CornellSphere cornell_load_sphere(const MRT_CONST_AS LinOp& so) {
     const MRT_CONST_AS uint32_t* q = reinterpret_cast<const MRT_CONST_AS uint32_t*>(&so);
-    return CornellSphere{q[4], q[5], q[6], q[12], q[3]};
+    return CornellSphere{q[4], q[5], q[6], q[12]};
 }
 MRT_DFN void cornell_take1(CornellBox& d) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+s"(d.s), "+s"(d.c), "+s"(d.o0), "+s"(d.o1), "+s"(d.o2), "+s"(d.mat));
+    asm volatile("" : "+s"(d.s), "+s"(d.c), "+s"(d.o0), "+s"(d.o1), "+s"(d.o2));
     asm volatile("" : "+s"(d.lo0), "+s"(d.lo1), "+s"(d.lo2), "+s"(d.hi0), "+s"(d.hi1), "+s"(d.hi2));
 #else
     (void)d;
@@ -490,7 +507,7 @@ MRT_DFN void cornell_take1(CornellBox& d) {
 }
 MRT_DFN void cornell_take1(CornellSphere& d) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+s"(d.c0), "+s"(d.c1), "+s"(d.c2), "+s"(d.rad), "+s"(d.mat));
+    asm volatile("" : "+s"(d.c0), "+s"(d.c1), "+s"(d.c2), "+s"(d.rad));
 #else
     (void)d;
 #endif
@@ -511,12 +528,20 @@ MRT_DFN void cornell_take1(CornellRoom& d) {
     (void)d;
 #endif
 }
+// the room's corners and mask only (the Cornell walk: a face's material comes from the hit table)
+MRT_DFN void cornell_take_faces(CornellRoom& d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(d.lo0), "+s"(d.lo1), "+s"(d.lo2), "+s"(d.hi0), "+s"(d.hi1), "+s"(d.hi2), "+s"(d.mask));
+#else
+    (void)d;
+#endif
+}
 // The room's walls (ops 1, 2, 4, 5, 6) as one slab test: a ray that meets the box leaves it
 // through the face of its smallest far-plane distance; that face, if the room has it, is the
 // wall hit (front-facing: the walls face inward; any face the ray crosses going in is back-facing
 // and missed, rect.cpp:26-30).  Differs from the five rect tests by rounding at the room's edges.
-// (kRec false: the caller reads only the hit's code, distance and side -- room_walls_op -- so the
-// face's plane and material are not selected: sel3's asm would keep the dead selects alive)
+// (kRec true: the Cornell walk, which takes the face as the hit's identity; false: room_walls_op,
+// which reads the hit's code, distance and side)
 template <uint32_t F, bool kRec = true>
 MRT_DFN void cornell_room(const CornellRoom& d, const Ray& r, float tmin, CornellRec& w) {
     const float lo0 = __uint_as_float(d.lo0), lo1 = __uint_as_float(d.lo1), lo2 = __uint_as_float(d.lo2);
@@ -539,18 +564,12 @@ MRT_DFN void cornell_room(const CornellRoom& d, const Ray& r, float tmin, Cornel
     const uint32_t side = da > 0.0f ? 1u : 0u;
     const uint32_t face = a * 2u + side;
     const bool h = (tn <= tf) & (((d.mask >> face) & 1u) != 0u) & (tf >= tmin) & (tf <= w.closest);
-    // plane and material of the face by selects (a chain of compares with one index became a
-    // per-lane lookup table in scratch memory)
     w.closest = h ? tf : w.closest;
-    w.code = h ? 1u + a : w.code;
-    w.ns = h ? (side ? -1.0f : 1.0f) : w.ns;
     if constexpr (kRec) {
-        const bool up = side != 0u;
-        const float k = up ? sel3(a, hi0, hi1, hi2) : sel3(a, lo0, lo1, lo2);
-        const uint32_t m = __float_as_uint(up ? sel3(a, __uint_as_float(d.m1), __uint_as_float(d.m3), __uint_as_float(d.m5))
-                                              : sel3(a, __uint_as_float(d.m0), __uint_as_float(d.m2), __uint_as_float(d.m4)));
-        w.k = h ? k : w.k;
-        w.mat = h ? m : w.mat;
+        w.id = h ? kHitRoom + face : w.id;
+    } else {
+        w.code = h ? 1u + a : w.code;
+        w.ns = h ? (side ? -1.0f : 1.0f) : w.ns;
     }
 }
 // The room + mesh walk's walls (scenes 8 / 9, tolerance build): the room's slab test as above,
@@ -562,7 +581,7 @@ MRT_DFN void room_walls_op(const MRT_CONST_AS LinOp& e, const Ray& r, float tmin
     asm volatile("" : "+s"(face_ops));
 #endif
     cornell_take1(d);
-    CornellRec c{w.closest, 0.0f, 0.0f, 0u, 0u};
+    CornellRec c{w.closest, kHitNone, 0.0f, 0u};
     cornell_room<0u, false>(d, r, tmin, c);
     if (c.code != 0u) {  // per lane: the exit face's axis from the code, its side from the sign
         const uint32_t face = (c.code - 1u) * 2u + (c.ns < 0.0f ? 1u : 0u);
@@ -576,30 +595,9 @@ template <typename... D>
 MRT_DFN void cornell_take(D&... d) {
     (cornell_take1(d), ...);
 }
-template <uint32_t F, uint32_t PC>
-MRT_DFN void cornell_rect(const CornellRect& d, const Ray& r, float tmin, CornellRec& w) {
-    constexpr uint32_t KIND = kSigs[SIG_CORNELL].kind[PC];
-    static_assert(kSigs[SIG_CORNELL].op[PC] == LOP_PRIM && KIND != MRT_K_SPHERE, "Cornell shape: world rect");
-    constexpr uint32_t AX = KIND == MRT_K_XY ? 2u : KIND == MRT_K_XZ ? 1u : 0u;
-    LinOp o;
-    o.code = 0;  // (lin_prim_t reads the flags only under the exact contract's guards)
-    o.f[0] = __uint_as_float(d.b0);
-    o.f[1] = __uint_as_float(d.b1);
-    o.f[2] = __uint_as_float(d.b2);
-    o.f[3] = __uint_as_float(d.b3);
-    o.f[4] = __uint_as_float(d.k);
-    o.f[5] = __uint_as_float(d.ns);
-    float t;
-    const bool h = lin_prim_t<F, KIND>(o, r, tmin, w.closest, &t);
-    w.closest = h ? t : w.closest;
-    w.code = h ? 1u + AX : w.code;
-    w.k = h ? o.f[4] : w.k;
-    w.ns = h ? o.f[5] : w.ns;
-    w.mat = h ? d.mat : w.mat;
-}
 // The light (op 3) is tested ONCE per ray, when the ray is made: its t with the walk's tmin and no
 // upper bound, kCornellMiss for a miss.  The walk then only compares it with the room's hit
-// (cornell_rect's compare and tie rule), and a scattered ray's xz_rect::pdf_value reads its hit
+// (a rect test's compare and tie rule), and a scattered ray's xz_rect::pdf_value reads its hit
 // flag and distance from it (mrt_shade.h finish_scatter, DScene::light_once) instead of testing
 // the same rect a second time.
 static constexpr float kCornellTmin = 0.001f, kCornellMiss = -1.0f;  // (a hit's t is >= tmin > 0, or NaN)
@@ -630,28 +628,28 @@ MRT_DFN float cornell_sphere_inv_rad(const MRT_CONST_AS LinOp* prog) {
     return 0.0f;  // (unused: the record divides)
 #endif
 }
+// hits: the LDS byte address of the wave's copy of the hit table (wave-uniform; LStack::hits).
+// *M: the hit's material, as S.mats[rec.mat] read it (rec.mat itself is not set: nothing reads it)
 template <uint32_t F>
-MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, float tmin, float lt, float inv_rad, HitRec& rec) {
+MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, float tmin, float lt, float inv_rad, uint32_t hits,
+                              HitRec& rec, DMat* M) {
     constexpr const LinSig& G = kSigs[SIG_CORNELL];
     static_assert(G.op[7] == LOP_INST && G.kind[7] == MRT_K_TRROTY && G.op[8] == LOP_LIST && G.skip[8] == 15 &&
                       G.op[17] == LOP_PRIM && G.kind[17] == MRT_K_SPHERE,
                   "Cornell shape: translate(rotate_y(box)) at op 7, its six rects under op 8, the sphere at op 17");
-    CornellRec w{FLT_MAX_, 0.0f, 0.0f, 0u, 0u};
+    static_assert(!(F & FT_TEX), "the hit table keeps a material's constant colour only");
+    CornellRec w{FLT_MAX_, kHitNone, 0.0f, 0u};
     // the room's walls as one slab test (ops 1, 2, 4, 5, 6; cornell_room_fill), then the light
     // (op 3), the box and the sphere: their words in two batches of scalar loads
     static_assert(G.op[G.n - 1] == LOP_END, "the room is kept in the END op");
     CornellRoom dr = cornell_load_room(prog[G.n - 1]);
-    CornellRect d3 = cornell_load(prog[3]);
-    cornell_take(dr, d3);
+    cornell_take_faces(dr);
     cornell_room<F>(dr, r, tmin, w);
-    {  // the light: cornell_rect<F, 3>'s outcome from the ray's one test (cornell_light_t, made with this tmin)
+    {  // the light: a rect test's outcome from the ray's one test (cornell_light_t, made with this tmin)
         (void)tmin;
         const bool h = !(lt < 0.0f) & !(lt > w.closest);
         w.closest = h ? lt : w.closest;
-        w.code = h ? 2u : w.code;
-        w.k = h ? __uint_as_float(d3.k) : w.k;
-        w.ns = h ? __uint_as_float(d3.ns) : w.ns;
-        w.mat = h ? d3.mat : w.mat;
+        w.id = h ? kHitLight : w.id;
     }
     CornellBox db = cornell_load_box(prog[7], prog[8]);
     CornellSphere dsp = cornell_load_sphere(prog[17]);
@@ -672,13 +670,11 @@ MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, floa
     const float tn = fmaxf(fmaxf(nx, ny), nz);
     const float tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
     const bool hb = (tn <= tf) & (tn >= tmin) & (tn <= w.closest);
-    // the entry face: its axis, and its outward normal's sign (against the ray's direction there)
+    // the entry face: its axis, and whether the ray goes up it (the min plane, outward normal -1)
     const uint32_t bax = tn == nx ? 0u : (tn == ny ? 1u : 2u);
     const float bd = sel3(bax, dx, r.d.y, dz);
     w.closest = hb ? tn : w.closest;
-    w.code = hb ? 4u + bax : w.code;
-    w.ns = hb ? (bd > 0.0f ? -1.0f : 1.0f) : w.ns;
-    w.mat = hb ? db.mat : w.mat;
+    w.id = hb ? kHitBox + 2u * bax + (bd > 0.0f ? 1u : 0u) : w.id;
     // the sphere (op 17)
     LinOp so;
     so.code = 0;  // (a static sphere: F has no FT_MOVING)
@@ -690,42 +686,48 @@ MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, floa
         float t;
         const bool h = lin_prim_t<F, MRT_K_SPHERE>(so, r, tmin, w.closest, &t);
         w.closest = h ? t : w.closest;
-        w.code = h ? 7u : w.code;
-        w.mat = h ? dsp.mat : w.mat;
+        w.id = h ? kHitSphere : w.id;
     }
-    if (w.code == 0u) return false;
+    if (w.id == kHitNone) return false;
+    // the hit's entry of the wave's table: three 16-byte LDS reads at one per-lane address
+    const uint32_t at = hits + w.id * (kHitLdsWords * 4u);
+    const MRT_LDS_AS v4f* e = (const MRT_LDS_AS v4f*)(uintptr_t)at;
+    const v4f q0 = e[0], q1 = e[1], q2 = e[2];
+    const float k = q0.w;
+    const uint32_t code = __float_as_uint(q1.x);
+    M->kind = __float_as_uint(q1.y);
+    M->tex = MRT_NONE;
+    M->p = q1.z;
+    M->flags = __float_as_uint(q1.w);
+    M->col[0] = q2.x;
+    M->col[1] = q2.y;
+    M->col[2] = q2.z;
+    M->col[3] = q2.w;
     rec.t = w.closest;
-    rec.mat = w.mat;
     f3 p = eval(r, w.closest);
     // world rects: the point on the rect's plane (MRT_FAST_SNAP, lin_prim_rec_op)
-    p.x = w.code == 1u ? w.k : p.x;
-    p.y = w.code == 2u ? w.k : p.y;
-    p.z = w.code == 3u ? w.k : p.z;
-    if (w.code >= 4u && w.code <= 6u) {
+    p.x = code == 1u ? k : p.x;
+    p.y = code == 2u ? k : p.y;
+    p.z = code == 3u ? k : p.z;
+    if (code >= 4u && code <= 6u) {
         // a box face: the point in the box frame put on the face's plane, then back to the world
         // (as lin_prim_rec_op + lin_untransform do).  o + t d in the world frame lands up to ~1e-4
         // off the face (t from a reciprocal, |t| ~ 1e3), and a grazing inward light-sampling ray
         // from there re-enters the box at t > tmin: +0.35% rays (measured).
         const float t = w.closest;
         float px = ox + t * dx, py = my + t * r.d.y, pz = oz + t * dz;
-        const float pl = w.code == 4u ? (w.ns < 0.0f ? lo0 : hi0)
-                       : w.code == 5u ? (w.ns < 0.0f ? lo1 : hi1)
-                                      : (w.ns < 0.0f ? lo2 : hi2);
-        px = w.code == 4u ? pl : px;
-        py = w.code == 5u ? pl : py;
-        pz = w.code == 6u ? pl : pz;
+        px = code == 4u ? k : px;
+        py = code == 5u ? k : py;
+        pz = code == 6u ? k : pz;
         p = f3{(c * px + s * pz) + off0, py + off1, (c * pz - s * px) + off2};
     }
     rec.p = p;
-    const uint32_t a = w.code >= 4u ? w.code - 4u : w.code - 1u;
-    const float lx = a == 0u ? w.ns : 0.0f, ly = a == 1u ? w.ns : 0.0f, lz = a == 2u ? w.ns : 0.0f;
-    f3 n{lx, ly, lz};
-    if (w.code >= 4u) n = f3{c * lx + s * lz, ly, c * lz - s * lx};  // unrotate_rec's normal
+    f3 n{q0.x, q0.y, q0.z};  // a rect's one-hot normal; a box face's rotated back (unrotate_rec's normal)
 #if MRT_FAST_DIV && defined(__HIP_DEVICE_COMPILE__)
-    if (w.code == 7u) n = mulf(sub(p, f3{so.f[0], so.f[1], so.f[2]}), inv_rad);  // divf's product, its rcp taken once
+    if (code == 7u) n = mulf(sub(p, f3{so.f[0], so.f[1], so.f[2]}), inv_rad);  // divf's product, its rcp taken once
 #else
     (void)inv_rad;
-    if (w.code == 7u) n = divf(sub(p, f3{so.f[0], so.f[1], so.f[2]}), so.f[8]);
+    if (code == 7u) n = divf(sub(p, f3{so.f[0], so.f[1], so.f[2]}), so.f[8]);
 #endif
     rec.n = n;
     return true;
@@ -736,13 +738,16 @@ template <uint32_t F>
 static constexpr uint32_t kBox6Walk = (MRT_FAST_BOX && MRT_SIG_OF(F) == SIG_CORNELL && !(F & (FT_UV | FT_MOVING))) ? 1u : 0u;
 
 // scene_object::hit for a program of shape SIG (same contract as scene_hit_lin)
-// (lt, inv_rad: kBox6Walk kernels only -- cornell_light_t of r, made with this tmin; cornell_sphere_inv_rad)
+// (lt, inv_rad, M: kBox6Walk kernels only -- cornell_light_t of r, made with this tmin;
+// cornell_sphere_inv_rad; the hit's material, which those kernels take from the hit table at L.hits
+// instead of S.mats[rec.mat])
 template <uint32_t F>
-MRT_DFN bool scene_hit_sig(const DScene& S, Ray& r, float tmin, HitRec& rec, const LStack& L, float lt = 0.0f, float inv_rad = 0.0f) {
+MRT_DFN bool scene_hit_sig(const DScene& S, Ray& r, float tmin, HitRec& rec, const LStack& L, float lt = 0.0f, float inv_rad = 0.0f,
+                           DMat* M = nullptr) {
     constexpr uint32_t SIG = MRT_SIG_OF(F);
     constexpr bool INST = (F & FT_INST) != 0;
     if constexpr (kBox6Walk<F>) {  // (the shape implies MRT_F_BOX6 on op 8: lin_sig_of)
-        return cornell_fast_hit<F>(const_ptr(S.prog), r, tmin, lt, inv_rad, rec);
+        return cornell_fast_hit<F>(const_ptr(S.prog), r, tmin, lt, inv_rad, L.hits, rec, M);
     } else {
     if (INST) lin_save_ray(L, r);
     const MRT_CONST_AS LinOp* prog = const_ptr(S.prog);

@@ -19,6 +19,7 @@ struct SceneTables {
     uint32_t light_once = 0;            // Cornell shape whose one biased leaf is op 3's rect (DScene::light_once)
     std::vector<mrtd::LinOp> prog;      // linear hit program (empty + LOP_END when the graph has none)
     std::vector<mrtd::LinOp> prog_fast; // its tolerance-contract rewrite (lin_rewrite_fast: rooms, box.h lists)
+    std::vector<uint32_t> cornell_hits; // Cornell shape: kHitCount x kHitWords words (mrt_sig.h hit table), else empty
     uint32_t prog_ops = 0;
     uint32_t features = 0;              // FT_* | FT_LIN | shape id (mrt_sig.h)
     int max_frames = 0, max_rays = 0, max_mesh = 0;  // deepest stacks of the scene graph

@@ -594,6 +594,64 @@ static void biased_leaves(const mrt_scene_view* v, const std::vector<mrt_node>& 
     T->nbleaf = T->blist ? nodes[v->biased].b : 1u;
 }
 
+// Cornell shape: the hit table of the tolerance contract's walk (mrt_sig.h cornell_fast_hit; the
+// entry layout is described there) -- per hit identity what the walk's per-lane selects and its
+// record code computed for every ray, from the same program words with the same expressions:
+//   room face 2 a + side: plane hi / lo [a] and material m[2 a + side] of the END op
+//     (cornell_room_fill), normal sign side ? -1 : 1;
+//   the light: op 3's plane f[4], side f[5] and material;
+//   box face of axis a, the ray going up it or not: normal sign -1 / 1, the face's plane in the box
+//     frame lo / hi [a] (op 8's f[6..11]), the normal rotated back by rotate_y's (s, c) (op 7's
+//     f[6], f[7]) as unrotate_rec does -- every product has a factor 0 or +-1, so it is exact, and a
+//     contracted multiply-add gives the same bits (a denormal sine or cosine aside, which the
+//     kernel's build flushes to zero);
+//   the sphere: op 17's material (its normal is the ray's own).
+static void cornell_hit_fill(const std::vector<LinOp>& prog, const std::vector<DMat>& dmats, std::vector<uint32_t>* out) {
+    out->assign((size_t)kHitCount * kHitWords, 0u);
+    auto put = [&](uint32_t id, const float n[3], float k, uint32_t code, uint32_t mat) {
+        uint32_t* e = out->data() + (size_t)id * kHitWords;
+        const DMat m = mat < dmats.size() ? dmats[mat] : DMat{};  // (a face the room lacks: never hit)
+        const float f[12] = {n[0], n[1], n[2], k, 0.0f, 0.0f, m.p, 0.0f, m.col[0], m.col[1], m.col[2], m.col[3]};
+        memcpy(e, f, sizeof f);
+        e[4] = code;
+        e[5] = m.kind;
+        e[7] = m.flags;
+    };
+    auto one_hot = [](uint32_t a, float ns, float n[3]) {
+        n[0] = a == 0u ? ns : 0.0f;
+        n[1] = a == 1u ? ns : 0.0f;
+        n[2] = a == 2u ? ns : 0.0f;
+    };
+    const LinOp& e = prog[kSigs[SIG_CORNELL].n - 1];
+    for (uint32_t a = 0; a < 3; a++)
+        for (uint32_t side = 0; side < 2; side++) {
+            float n[3];
+            one_hot(a, side ? -1.0f : 1.0f, n);
+            uint32_t mat;
+            memcpy(&mat, &e.f[6 + a * 2 + side], 4);
+            put(kHitRoom + a * 2 + side, n, side ? e.f[3 + a] : e.f[a], 1u + a, mat);
+        }
+    {
+        const LinOp& l = prog[3];
+        float n[3];
+        one_hot(1u, l.f[5], n);
+        put(kHitLight, n, l.f[4], 2u, l.mat);
+    }
+    const LinOp &io = prog[7], &bo = prog[8];
+    const float s = io.f[6], c = io.f[7];
+    for (uint32_t a = 0; a < 3; a++)
+        for (uint32_t up = 0; up < 2; up++) {
+            const float ns = up ? -1.0f : 1.0f;
+            float l[3];
+            one_hot(a, ns, l);
+            const float lx = l[0], ly = l[1], lz = l[2];
+            const float n[3] = {c * lx + s * lz, ly, c * lz - s * lx};
+            put(kHitBox + 2 * a + up, n, ns < 0.0f ? bo.f[6 + a] : bo.f[9 + a], 4u + a, bo.mat);
+        }
+    const float none[3] = {0.0f, 0.0f, 0.0f};
+    put(kHitSphere, none, 0.0f, 7u, prog[17].mat);
+}
+
 // The linear hit program (LinCompiler; empty + LOP_END when the graph has none or MRT_FORCE_GENERIC
 // is set) and what follows from it: FT_LIN / FT_VSUB and the shape id (not under MRT_NO_SIG) into
 // T->features, light_once (reads T->bleaf), the tolerance contract's rewrite.
@@ -613,6 +671,7 @@ static void linear_program(const mrt_scene_view* v, const std::vector<mrt_node>&
         T->light_once = (MRT_SIG_OF(T->features) == SIG_CORNELL && v->biased != MRT_NONE && T->bleaf.size() == 1 &&
                          (T->bleaf[0].kind & 0xFF) == MRT_K_XZ && memcmp(T->bleaf[0].f, lc.prog[3].f, 6 * sizeof(float)) == 0)
                             ? 1u : 0u;
+        if (MRT_SIG_OF(T->features) == SIG_CORNELL) cornell_hit_fill(lc.prog, T->dmats, &T->cornell_hits);
         T->prog_fast = lin_rewrite_fast(lc.prog);
     }
     T->prog.swap(lc.prog);
@@ -656,6 +715,16 @@ extern "C" int mrt_debug_lin_program(const mrt_scene_view* v, int rewritten, uin
         codes[i] = p[i].code;
         skips[i] = p[i].skip;
     }
+    return 0;
+}
+
+// Test hook (tests/test_cornell_hit_table.py): the Cornell walk's hit table as built for the view,
+// *n its words (0: the view has no Cornell shape), the first min(cap, *n) copied out.
+extern "C" int mrt_debug_cornell_hits(const mrt_scene_view* v, uint32_t* words, uint32_t cap, uint32_t* n) {
+    SceneTables T;
+    if (mrt_internal_scene_tables(v, &T) != MRT_OK) return 1;
+    *n = (uint32_t)T.cornell_hits.size();
+    memcpy(words, T.cornell_hits.data(), std::min<size_t>(cap, T.cornell_hits.size()) * 4);
     return 0;
 }
 

@@ -217,6 +217,7 @@ struct LStack {
     uint32_t lane;
     const float4* tree;  // the workgroup's LDS copy of BvhWide nodes [0, tree_b) (TreeOf<F>::on kernels)
     uint32_t tree_b;
+    uint32_t hits = 0;   // LDS byte address of the wave's Cornell hit table (mrt_sig.h; kBox6Walk kernels)
 };
 
 // Hot BVH nodes in LDS (north star): kernels of the bvh_node scenes run two 12-wave workgroups
