@@ -262,7 +262,12 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                     TreeOf<F>::on ? P.tree_n : 0u,
                     !kBox6Walk<F> ? 0u
                     : TreeOf<F>::wg == 64u ? (uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)lds  // (one wave: its slice is the group's)
-                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(wb - hit_words))};
+                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(wb - hit_words)),
+                    // (the basis axes of the table's normals: in the claim row of the queue below, mrt_sig.h kHitAxisWord0)
+                    !kBox6Walk<F> ? 0u
+                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(
+                          wmesh + (P.lds_mesh + P.lds_save + LK * 4 + 12u) * 64 + kHitAxisWord0))};
+    static_assert(!kBox6Walk<F> || PathQ<F>::on, "the Cornell walk's basis axes live in the queue's claim row");
     // the wave's queue of path starts ([word][entry], PathQ): after the fold levels
     float* const Lq = (float*)(wmesh + (P.lds_mesh + P.lds_save + LK * 4) * 64);
     const DScene& S = P.sc;
@@ -495,7 +500,16 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             const uint32_t e = lane / 3u, qd = lane - e * 3u;
             if (lane < kHitCount * (kHitLdsWords / 4u)) {
                 const v4f* src = reinterpret_cast<const v4f*>(S.prog + kSigs[SIG_CORNELL].n) + e * (kHitWords / 4u) + qd;
-                ((MRT_LDS_AS v4f*)(uintptr_t)Ls.hits)[lane] = *src;
+                const v4f q = *src;
+                ((MRT_LDS_AS v4f*)(uintptr_t)Ls.hits)[lane] = q;
+                // the lane that holds an entry's normal (quad 0) also makes its basis axis v, with the
+                // per-lane basis' own function on the same bits, into the wave's axes (trace_split's
+                // diffuse branch reads it by identity; the sphere's entry has no normal, its quad is not used).
+                // The claim state beside it is words 0-4 of the row, written by lane 0 above.
+                if (qd == 0u) {
+                    const f3 v = onb_axis_v(f3{q.x, q.y, q.z});
+                    ((MRT_LDS_AS v4f*)(uintptr_t)Ls.axes)[e] = v4f{v.x, v.y, v.z, 0.0f};
+                }
             }
         }
         for (;;) {
@@ -562,6 +576,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                             claim(64u, lane, true, &i);
                             cold_store();
                             const bool valid = i < P.n_paths;
+                            BSTATC(17, valid);
                             if (valid) {
                                 BSTAT(10);
                                 Pcg rng;

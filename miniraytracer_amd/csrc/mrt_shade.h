@@ -79,13 +79,19 @@ MRT_DFN f3 mat_color(const DScene& S, const DMat& M, const HitRec& rec) {
     return tex_sample<F>(S, M.tex, rec.u, rec.v, rec.p);
 }
 
-// onb(n) * vec (onb.h:19-27)
-MRT_DFN f3 onb_apply(f3 w, f3 vec) {
+// onb(n) (onb.h:19-24) in two steps: the axis v, a function of the normal alone (the axis select, a
+// cross product, the normalize), and u from w and v
+MRT_DFN f3 onb_axis_v(f3 w) {
     f3 a = fabsf(w.x) > 0.9f ? f3{0, 1, 0} : f3{1, 0, 0};
-    f3 v = normalize(cross(w, a));
+    return normalize(cross(w, a));
+}
+// (u, v, w) * vec (onb.h:26-27)
+MRT_DFN f3 onb_local(f3 w, f3 v, f3 vec) {
     f3 u = cross(w, v);
     return add(add(fmul(vec.x, u), fmul(vec.y, v)), fmul(vec.z, w));
 }
+// onb(n) * vec (onb.h:19-27)
+MRT_DFN f3 onb_apply(f3 w, f3 vec) { return onb_local(w, onb_axis_v(w), vec); }
 
 // The next randf() values of a path's stream, two of them drawn ahead: every direction generator
 // of the lambertian mix starts with two draws, so they are drawn once before the light/surface
@@ -598,7 +604,8 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     Ray& r = ps.r;
     bool hit;
     DMat M;  // the hit's material: the Cornell fast walk reads it from its hit table, with the record
-    if constexpr (kBox6Walk<F>) hit = scene_hit_sig<F>(S, r, kCornellTmin, rec, Ls, ps.lt, inv_rad, &M);  // (ps.lt: set where the path loop makes r)
+    uint32_t hid = 0;  // ... and hands out the hit's identity (mrt_sig.h kHit*)
+    if constexpr (kBox6Walk<F>) hit = scene_hit_sig<F>(S, r, kCornellTmin, rec, Ls, ps.lt, inv_rad, &M, &hid);  // (ps.lt: set where the path loop makes r)
     else if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, r, 0.001f, rec, Ls);
     else if constexpr ((F & FT_LIN) != 0) hit = scene_hit_lin<F>(S, r, 0.001f, rec, Ls, ps.rng, ph);
     else hit = scene_hit<F>(S, r, 0.001f, rec, ps.rng, Ls);
@@ -662,6 +669,16 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     }
     pr->kind = lamb ? 1u : 2u;
     BSTAT(6);
+    // Cornell fast walk: the basis axis v of a table normal is a constant of the hit's identity, read
+    // from the wave's LDS (mrt_sig.h kHitAxisWords) instead of built per lane on the cosine side -- the
+    // axis select, a cross product and a normalize at ~18 lanes of 64.  Issued here, by every diffuse
+    // lane before the draws, so the draws cover its latency (one instruction at any lane count; the
+    // sphere's quad is in bounds and not used).  The whole quad, one ds_read_b128 (three words as a
+    // ds_read_b96 ran into LDS bank conflicts, measured), its unused fourth register kept allocated up
+    // to the use below: reused at once, its write-after-write hazard made the code wait for the read
+    // right here.
+    v4f axq{0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (kBox6Walk<F>) axq = *(const MRT_LDS_AS v4f*)(uintptr_t)(Ls.axes + hid * (kHitAxisWords * 4u));
     const bool light = ((F & FT_BIASED) && S.biased != MRT_NONE) && randf(ps.rng) < 0.5f;
     Draws dr{0.0f, 0.0f, 2u};
     if (lamb && predraw_ok<F>(S, light)) {
@@ -670,8 +687,23 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
         dr.used = 0;
     }
     BSTATC(7, light);
-    if (light) pr->dir = biased_pdf_generate<F>(S, rec.p, r.time, ps.rng, dr);
-    else pr->dir = lamb ? onb_apply(rec.n, random_cosine_direction_pre(dr.v0, dr.v1)) : random_in_sphere(ps.rng);
+    if (light) {
+        pr->dir = biased_pdf_generate<F>(S, rec.p, r.time, ps.rng, dr);
+    } else if constexpr (kBox6Walk<F>) {
+        if (lamb) {
+            const f3 vec = random_cosine_direction_pre(dr.v0, dr.v1);
+            f3 v{axq.x, axq.y, axq.z};
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" ::"v"(axq.w));  // (the quad's fourth register stays allocated until here)
+#endif
+            if (hid == kHitSphere) v = onb_axis_v(rec.n);  // the sphere's normal is the ray's own: the per-lane axis
+            pr->dir = onb_local(rec.n, v, vec);
+        } else {
+            pr->dir = random_in_sphere(ps.rng);
+        }
+    } else {
+        pr->dir = lamb ? onb_apply(rec.n, random_cosine_direction_pre(dr.v0, dr.v1)) : random_in_sphere(ps.rng);
+    }
     crit_check(cs, light, rec.p, pr->dir, dr.edge, rec.n);  // listed: retraced with the exact arithmetic
     PH_MARK(ph, 6);
     return false;

@@ -463,6 +463,14 @@ enum : uint32_t { kHitRoom = 0, kHitLight = 6, kHitBox = 7, kHitSphere = 13, kHi
 static constexpr uint32_t kHitWords = 16, kHitLdsWords = 12;
 static constexpr uint32_t kHitLdsBytes = kHitCount * kHitLdsWords * 4;  // 672 per wave
 static_assert(sizeof(LinOp) == kHitWords * 4 && kHitLdsBytes % 16 == 0, "hit table entries are uploaded as trailing ops");
+// The cosine scatter's basis axis v of each entry's normal (mrt_shade.h onb_axis_v: the axis select,
+// a cross product and a normalize that depend on the hit's identity alone), one quad (v, 0) per
+// identity.  Each wave computes them once from its copy of the table, with the function the per-lane
+// basis uses, and keeps them in the row of its path-start queue that holds the claim state (words 0-4
+// of 64, mrt_kernels.hip): quads at words 8 + 4 i, 56 consecutive words -- no two in one bank, any
+// mix of identities reads without a conflict -- and no LDS beyond what the wave had.
+static constexpr uint32_t kHitAxisWord0 = 8, kHitAxisWords = 4;
+static_assert(kHitAxisWord0 % 4 == 0 && kHitAxisWord0 + kHitCount * kHitAxisWords <= 64, "the axes fit the claim row, 16-byte aligned");
 struct CornellRec {
     float closest;
     uint32_t id;    // cornell_fast_hit: the hit's identity (kHitNone: none)
@@ -630,9 +638,10 @@ MRT_DFN float cornell_sphere_inv_rad(const MRT_CONST_AS LinOp* prog) {
 }
 // hits: the LDS byte address of the wave's copy of the hit table (wave-uniform; LStack::hits).
 // *M: the hit's material, as S.mats[rec.mat] read it (rec.mat itself is not set: nothing reads it)
+// *hid: the hit's identity (the cosine scatter's index into the wave's basis axes, kHitAxisWords)
 template <uint32_t F>
 MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, float tmin, float lt, float inv_rad, uint32_t hits,
-                              HitRec& rec, DMat* M) {
+                              HitRec& rec, DMat* M, uint32_t* hid) {
     constexpr const LinSig& G = kSigs[SIG_CORNELL];
     static_assert(G.op[7] == LOP_INST && G.kind[7] == MRT_K_TRROTY && G.op[8] == LOP_LIST && G.skip[8] == 15 &&
                       G.op[17] == LOP_PRIM && G.kind[17] == MRT_K_SPHERE,
@@ -689,6 +698,7 @@ MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, floa
         w.id = h ? kHitSphere : w.id;
     }
     if (w.id == kHitNone) return false;
+    *hid = w.id;
     // the hit's entry of the wave's table: three 16-byte LDS reads at one per-lane address
     const uint32_t at = hits + w.id * (kHitLdsWords * 4u);
     const MRT_LDS_AS v4f* e = (const MRT_LDS_AS v4f*)(uintptr_t)at;
@@ -738,16 +748,16 @@ template <uint32_t F>
 static constexpr uint32_t kBox6Walk = (MRT_FAST_BOX && MRT_SIG_OF(F) == SIG_CORNELL && !(F & (FT_UV | FT_MOVING))) ? 1u : 0u;
 
 // scene_object::hit for a program of shape SIG (same contract as scene_hit_lin)
-// (lt, inv_rad, M: kBox6Walk kernels only -- cornell_light_t of r, made with this tmin;
+// (lt, inv_rad, M, hid: kBox6Walk kernels only -- cornell_light_t of r, made with this tmin;
 // cornell_sphere_inv_rad; the hit's material, which those kernels take from the hit table at L.hits
-// instead of S.mats[rec.mat])
+// instead of S.mats[rec.mat]; the hit's identity)
 template <uint32_t F>
 MRT_DFN bool scene_hit_sig(const DScene& S, Ray& r, float tmin, HitRec& rec, const LStack& L, float lt = 0.0f, float inv_rad = 0.0f,
-                           DMat* M = nullptr) {
+                           DMat* M = nullptr, uint32_t* hid = nullptr) {
     constexpr uint32_t SIG = MRT_SIG_OF(F);
     constexpr bool INST = (F & FT_INST) != 0;
     if constexpr (kBox6Walk<F>) {  // (the shape implies MRT_F_BOX6 on op 8: lin_sig_of)
-        return cornell_fast_hit<F>(const_ptr(S.prog), r, tmin, lt, inv_rad, L.hits, rec, M);
+        return cornell_fast_hit<F>(const_ptr(S.prog), r, tmin, lt, inv_rad, L.hits, rec, M, hid);
     } else {
     if (INST) lin_save_ray(L, r);
     const MRT_CONST_AS LinOp* prog = const_ptr(S.prog);

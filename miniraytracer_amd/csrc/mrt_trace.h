@@ -218,6 +218,7 @@ struct LStack {
     const float4* tree;  // the workgroup's LDS copy of BvhWide nodes [0, tree_b) (TreeOf<F>::on kernels)
     uint32_t tree_b;
     uint32_t hits = 0;   // LDS byte address of the wave's Cornell hit table (mrt_sig.h; kBox6Walk kernels)
+    uint32_t axes = 0;   // ... and of its table of basis axes, one quad per hit identity (mrt_sig.h kHitAxisWords)
 };
 
 // Hot BVH nodes in LDS (north star): kernels of the bvh_node scenes run two 12-wave workgroups

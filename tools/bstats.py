@@ -19,7 +19,8 @@ v = np.array(list(out), dtype=np.float64).reshape(32, 2)
 names = {0: "shade entry", 1: "miss", 2: "light", 3: "depth end", 4: "metal", 5: "dielectric", 6: "diffuse",
          7: "diffuse: light-sampled (cond)", 8: "instance reached (cond in)", 9: "instance body (cond in)",
          10: "new path", 11: "box6 reached (cond in)", 12: "make_ray (cond finish_scatter)", 14: "shade entry (cond hit)",
-         15: "make_ray reached (cond active)"}
+         15: "make_ray reached (cond active)", 16: "camera disk attempt (a trip of the rejection loop)",
+         17: "queue refill (cond: lanes with a new path)"}
 print(f"scene {scene} {w}x{h}x{spp}: rays {rays}")
 for i, (ex, ln) in enumerate(v):
     if ex:
