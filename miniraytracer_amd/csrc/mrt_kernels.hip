@@ -15,6 +15,7 @@
 // is written sample-major [s][local pixel] (coalesced).
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <type_traits>
 #include <utility>
 
 #include "mrt_launch.h"
@@ -229,6 +230,18 @@ MRT_DFN const DScene& kernarg_scene() {
     asm volatile("" : "+s"(sp));
     return *(const DScene*)sp;
 }
+// the same for the whole argument struct: what only a refill of the Cornell kernels' queue of path
+// starts reads (the path key's and the claim's parameters, the camera's address) is scalar-loaded
+// there, once per 64 starts, instead of held in SGPRs across the path loop
+MRT_DFN const PathParams& kernarg_params() {
+    const MRT_CONST_AS PathParams* pp = (const MRT_CONST_AS PathParams*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pp));
+    return *(const PathParams*)pp;
+}
+// claim()'s arguments: P, or the pointer a refill hands it (an optional trailing argument: as a plain
+// reference parameter it reordered two register copies in the exact build's kernels)
+MRT_DFN const PathParams& claim_params(const PathParams& P) { return P; }
+MRT_DFN const PathParams& claim_params(const PathParams&, const PathParams* q) { return *q; }
 #ifndef MRT_OPAQUE_RESUME
 #define MRT_OPAQUE_RESUME 0  // the same in the room + mesh kernels' resumable loop: measured C3 -0.6%, C4 0 (A/B hook)
 #endif
@@ -355,23 +368,25 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     auto path_key = [&](uint32_t i, Pcg& rng, float* uo, float* vo) { path_key_of(P, i, rng, uo, vo); };
     // the next c path indices of the wave's pool, the lane of rank r taking index *i (>= n_paths:
     // none); the pool refilled by one atomic per claim (work_queue::getWork, work_queue.cpp:158-166)
-    auto claim = [&](uint32_t c, uint32_t r, bool want, uint64_t* i) {
+    // (q: where a refill of a Cornell walk kernel reads the kernel's arguments, kernarg_params(); else P)
+    auto claim = [&](uint32_t c, uint32_t r, bool want, uint64_t* i, auto... q) {
+        const PathParams& Q = claim_params(P, q...);
         const uint32_t have = (uint32_t)(pool_end - pool_next);
         uint64_t nb = 0, ne = 0;
         if (have < c) {
             while (part_tries < MRT_STEAL_TRIES) {  // wave-uniform
-                const uint64_t pe = P.part_base[part + 1], p0 = P.part_dyn[part];
+                const uint64_t pe = Q.part_base[part + 1], p0 = Q.part_dyn[part];
                 const uint32_t batch = in_tail ? MRT_TAIL_BATCH : MRT_BATCH;
 #if defined(MRT_EXPERIMENTS) && defined(MRT_WTIMES)
                 uint64_t wt_a = 0;
                 WT_MARK(wt_a);
 #endif
                 if (lane == 0) {
-                    nb = p0 + atomicAdd(P.counter + part * MRT_COUNTER_STRIDE, (unsigned long long)batch);
+                    nb = p0 + atomicAdd(Q.counter + part * MRT_COUNTER_STRIDE, (unsigned long long)batch);
                     // every 32nd claim: a system-scope store to host memory, read by mrt_progress
                     // without any GPU queue (a device-to-host copy could wait behind this launch)
-                    if (P.hprog && (((nb - p0) / batch) & 31u) == 0)
-                        __hip_atomic_store(P.hprog + part, nb + batch - P.part_base[part], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    if (Q.hprog && (((nb - p0) / batch) & 31u) == 0)
+                        __hip_atomic_store(Q.hprog + part, nb + batch - Q.part_base[part], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
                 // lane 0's claim to every lane, as a scalar (the whole wave runs claim())
                 nb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(nb >> 32)) << 32) |
@@ -388,9 +403,9 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                     ne = umin64(nb + batch, pe);
                     // near the partition's end, claims shrink so the last ones finish together
 #if MRT_STEAL_SMALL
-                    in_tail = pe - ne <= P.tail_zone / MRT_NPART;
+                    in_tail = pe - ne <= Q.tail_zone / MRT_NPART;
 #else
-                    in_tail = in_tail || pe - ne <= P.tail_zone / MRT_NPART;
+                    in_tail = in_tail || pe - ne <= Q.tail_zone / MRT_NPART;
 #endif
                     break;
                 }
@@ -491,8 +506,14 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
         bool st_pend = false;
         // Cornell fast walk: the sphere's 1 / radius, once per launch (mrt_sig.h cornell_sphere_inv_rad)
         float sph_inv_rad = 0.0f;
+        // ... and the walk's scene words and the depth limit, held in scalar registers for the launch
+        // (mrt_sig.h CornellWords)
+        std::conditional_t<kBox6Walk<F> != 0u, CornellWords, NoCornellWords> cw{};
         if constexpr (kBox6Walk<F>) {
             sph_inv_rad = cornell_sphere_inv_rad(const_ptr(S.prog));
+            cw = cornell_words(const_ptr(S.prog), P.max_bounces,
+                               (S.biased != MRT_NONE ? 1u << kCwBiased : 0u) | (S.light_once ? 1u << kCwLightOnce : 0u) |
+                                   (S.blist ? 1u << kCwBlist : 0u) | (P.path_rays ? 1u << kCwPathRays : 0u));
             // the scene's hit table (kHitCount entries behind the program's END op, mrt_tables.hip
             // cornell_hit_fill) into the wave's LDS: the first three 16-byte quads of each entry, one
             // per lane, packed (entry e's quad q lands at quad 3 e + q = the lane).  Only this wave
@@ -513,6 +534,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             }
         }
         for (;;) {
+            if constexpr (kBox6Walk<F>) cornell_words_hold(cw);
             bool want_ray = false;
             // the next ray's arguments: written and read within one iteration (declared here, a
             // field a branch leaves unset is dead, not carried round the loop in copied registers)
@@ -520,7 +542,9 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             if (active) {
                 f3 L{0.0f, 0.0f, 0.0f};  // (left undefined, it was carried round the loop in copied registers)
                 // (the held store is issued inside, after the hit, beside the material load)
-                const bool ended = trace_split<F, LK>(S, ps, P.max_bounces, lev, Ls, &L, &pr, ph, [&]() {
+                uint32_t max_bounces = P.max_bounces;
+                if constexpr (kBox6Walk<F>) max_bounces = cw.max_bounces;
+                const bool ended = trace_split<F, LK>(S, ps, max_bounces, lev, Ls, &L, &pr, ph, [&]() {
                     if (st_pend) {
                         float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off);
                         dst[0] = st_v.x;
@@ -528,13 +552,15 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                         dst[2] = st_v.z;
                     }
                     st_pend = false;
-                }, CritSink{idx, kCritOff<F>}, sph_inv_rad);
+                }, CritSink{idx, kCritOff<F>}, sph_inv_rad, cornell_ptr(cw));
                 PH_MARK(ph, 2);
                 if (ended) {
                     st_v = end_path(ps, lev, L);
                     st_off = idx * 12u;
                     st_pend = true;
-                    if (P.path_rays) P.path_rays[idx] = ps.rays();
+                    if constexpr (kBox6Walk<F>) {
+                        if (cornell_flag(&cw, kCwPathRays)) kernarg_params().path_rays[idx] = ps.rays();
+                    } else if (P.path_rays) P.path_rays[idx] = ps.rays();
                     done_rays += ps.rays();
                     active = false;
                 } else {
@@ -572,18 +598,21 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                         q_head = q_n = 0;
                         if (!exhausted) {
                             uint64_t i = 0;
+                            // (a Cornell walk kernel reads the refill's parameters here, not across the loop)
+                            const PathParams& Q = kBox6Walk<F> ? kernarg_params() : P;
                             cold_load();
-                            claim(64u, lane, true, &i);
+                            if constexpr (kBox6Walk<F>) claim(64u, lane, true, &i, &Q);
+                            else claim(64u, lane, true, &i);
                             cold_store();
-                            const bool valid = i < P.n_paths;
+                            const bool valid = i < Q.n_paths;
                             BSTATC(17, valid);
                             if (valid) {
                                 BSTAT(10);
                                 Pcg rng;
                                 float u, v, time;
                                 f3 o, dir;
-                                path_key((uint32_t)i, rng, &u, &v);
-                                camera_ray_args(S, rng, u, v, &o, &dir, &time);
+                                path_key_of(Q, (uint32_t)i, rng, &u, &v);
+                                camera_ray_args(Q.sc, rng, u, v, &o, &dir, &time);
                                 float* q = Lq + lane;
                                 q[0] = o.x; q[64] = o.y; q[128] = o.z;
                                 q[192] = dir.x; q[256] = dir.y; q[320] = dir.z;
@@ -626,9 +655,9 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                 ps.r = make_ray(pr.o, pr.dir, pr.time, pr.inside);
                 // the Cornell fast walk's light test, once per ray: the scatter's light pdf below and
                 // the next iteration's walk both read it (one VGPR across the back edge)
-                if constexpr (kBox6Walk<F>) ps.lt = cornell_light_t<F>(const_ptr(S.prog), ps.r);
+                if constexpr (kBox6Walk<F>) ps.lt = cornell_light_t<F>(cw.light, ps.r);
                 PH_MARK(ph, 8);
-                if (pr.kind) finish_scatter<F, LK>(S, ps, lev, pr);
+                if (pr.kind) finish_scatter<F, LK>(S, ps, lev, pr, cornell_ptr(cw));
             }
             PH_MARK(ph, 7);
         }

@@ -48,6 +48,8 @@ struct PathParams {
     RetraceList rt;
 };
 
+static_assert(offsetof(PathParams, sc) == kSceneArgOffset, "mrt_shade.h cold_scene reads the scene from the argument segment");
+
 typedef void (*path_kernel_t)(PathParams);
 
 // path index -> (local pixel, sample row of the chunk): i = sl * npix + lp

@@ -145,6 +145,35 @@ MRT_DFN float leaf_pdf_value(const DScene& S, const mrt_node& n, f3 origin, f3 d
     return 0;
 }
 
+// The scene's arguments for code a Cornell walk kernel runs rarely or never (a biased list that is not
+// the walk's light): through an opaque constant pointer, so its fields are scalar-loaded where they are
+// used instead of held in SGPRs across the path loop.  Other kernels: S itself.
+// (the scene is the first member of the path kernels' only argument: mrt_launch.h asserts the offset)
+static constexpr uint32_t kSceneArgOffset = 0u;
+template <uint32_t F>
+MRT_DFN const DScene& cold_scene(const DScene& S) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (kBox6Walk<F>) {
+        const MRT_CONST_AS DScene* sp =
+            (const MRT_CONST_AS DScene*)((const MRT_CONST_AS char*)__builtin_amdgcn_kernarg_segment_ptr() + kSceneArgOffset);
+        asm volatile("" : "+s"(sp));
+        return *(const DScene*)sp;
+    }
+#endif
+    return S;
+}
+// the scene has a biased list / its one leaf is the Cornell walk's light (a Cornell walk kernel reads
+// the launch's flag word, mrt_sig.h CornellWords)
+template <uint32_t F>
+MRT_DFN bool has_biased(const DScene& S, const CornellWords* cw) {
+    if constexpr (kBox6Walk<F>) return cornell_flag(cw, kCwBiased);
+    else return S.biased != MRT_NONE;
+}
+template <uint32_t F>
+MRT_DFN bool light_once(const DScene& S, const CornellWords* cw) {
+    if constexpr (kBox6Walk<F>) return cornell_flag(cw, kCwLightOnce);
+    else return false;
+}
 // object_list::pdf_value over the biased list (scene_object.h:64-70): the leaves are read through
 // the constant address space (uniform index: scalar loads, no node -> children -> node chain)
 template <uint32_t F>
@@ -189,14 +218,14 @@ MRT_DFN f3 leaf_pdf_generate(const DScene& S, const mrt_node& n, f3 origin, floa
     return f3{1, 0, 0};
 }
 template <uint32_t F>
-MRT_DFN f3 biased_pdf_generate(const DScene& S, f3 origin, float time, Pcg& rng, Draws& dr) {
+MRT_DFN f3 biased_pdf_generate(const DScene& S0, f3 origin, float time, Pcg& rng, Draws& dr, const CornellWords* cw = nullptr) {
     if constexpr (kBox6Walk<F>) {
         // the one biased leaf is op 3's rect bit for bit (DScene::light_once): xz_rect::pdf_generate
-        // from the program's words, one batch of scalar loads at a constant offset -- the leaf's kind
-        // word and then, after a wait, its bounds were two dependent round trips
-        if (S.light_once) {
-            if (S.blist) (void)dr.next(rng);  // object_list::pdf_generate's index draw (scene_object.h:72-77)
-            const CornellRect d = cornell_load(const_ptr(S.prog)[3]);
+        // from the program's words, which the launch holds in scalar registers (mrt_sig.h CornellWords)
+        // -- the leaf's kind word and then, after a wait, its bounds were two dependent round trips
+        if (light_once<F>(S0, cw)) {
+            if (cornell_flag(cw, kCwBlist)) (void)dr.next(rng);  // object_list::pdf_generate's index draw (scene_object.h:72-77)
+            const CornellRect& d = cw->light;
             mrt_node n;
             n.kind = MRT_K_XZ;
             n.f[0] = __uint_as_float(d.b0);
@@ -204,9 +233,10 @@ MRT_DFN f3 biased_pdf_generate(const DScene& S, f3 origin, float time, Pcg& rng,
             n.f[2] = __uint_as_float(d.b2);
             n.f[3] = __uint_as_float(d.b3);
             n.f[4] = __uint_as_float(d.k);
-            return leaf_pdf_generate<F>(S, n, origin, time, rng, dr);
+            return leaf_pdf_generate<F>(S0, n, origin, time, rng, dr);
         }
     }
+    const DScene& S = cold_scene<F>(S0);  // (the list's fields, read where they are used)
     if (!S.blist) {
         const mrt_node n = ld_node(const_ptr(S.bleaf));
         return leaf_pdf_generate<F>(S, n, origin, time, rng, dr);
@@ -555,7 +585,13 @@ struct PendRay {
 
 // dielectric::scatter (material.h:121-175) of a hit with normal n for ray r: the next ray's
 // direction and inside count in *pr (its origin and time are set by the caller)
-MRT_DFN void dielectric_scatter(const DMat& M, const Ray& r, f3 n, Pcg& rng, PendRay* pr) {
+// pd: the stream's next draw made ahead by the caller (trace_split's Cornell walk), or null: the draw
+// is made here.  Either way the stream moves on only where the reflect test is made.
+struct PreDraw {
+    float v;         // randf of the stream's next output
+    uint64_t state;  // the stream's state after it
+};
+MRT_DFN void dielectric_scatter(const DMat& M, const Ray& r, f3 n, Pcg& rng, PendRay* pr, const PreDraw* pd = nullptr) {
     const float ref = M.p;
     const float cosI = -dot(r.d, n);
     f3 facing;
@@ -578,7 +614,14 @@ MRT_DFN void dielectric_scatter(const DMat& M, const Ray& r, f3 n, Pcg& rng, Pen
         const float cs = cosI < 0 ? sqrt_(ref_fnma(nio * nio, ref_fnma(cosI, cosI, 1.0f), 1.0f)) : cosI;
         const float r0 = M.col[1];  // ((1 - ref) / (1 + ref))^2, computed on upload
         const float reflect_prob = ref_fma(1 - r0, pow5_((1 - cs)), r0);
-        if (!(randf(rng) < reflect_prob)) {
+        float x;
+        if (pd) {
+            x = pd->v;
+            rng.state = pd->state;
+        } else {
+            x = randf(rng);
+        }
+        if (!(x < reflect_prob)) {
             nd = add(fmul(nio, r.d), fmul(ref_fms(nio, -ncosI, cosT), facing));
             if (cosI < 0) {
                 inside--;
@@ -599,13 +642,13 @@ MRT_DFN void dielectric_scatter(const DMat& M, const Ray& r, f3 n, Pcg& rng, Pen
 template <uint32_t F, uint32_t LK, typename FLUSH>
 MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, const LevStore<LK>& lev,
                                             const LStack& Ls, f3* L, PendRay* pr, PhaseClock& ph, FLUSH&& flush, const CritSink& cs = CritSink{0u, 0u},
-                                            float inv_rad = 0.0f) {
+                                            float inv_rad = 0.0f, const CornellWords* cw = nullptr) {
     HitRec rec;
     Ray& r = ps.r;
     bool hit;
     DMat M;  // the hit's material: the Cornell fast walk reads it from its hit table, with the record
     uint32_t hid = 0;  // ... and hands out the hit's identity (mrt_sig.h kHit*)
-    if constexpr (kBox6Walk<F>) hit = scene_hit_sig<F>(S, r, kCornellTmin, rec, Ls, ps.lt, inv_rad, &M, &hid);  // (ps.lt: set where the path loop makes r)
+    if constexpr (kBox6Walk<F>) hit = scene_hit_sig<F>(S, r, kCornellTmin, rec, Ls, ps.lt, inv_rad, &M, &hid, cw);  // (ps.lt: set where the path loop makes r)
     else if constexpr (MRT_SIG_OF(F) != SIG_NONE) hit = scene_hit_sig<F>(S, r, 0.001f, rec, Ls);
     else if constexpr ((F & FT_LIN) != 0) hit = scene_hit_lin<F>(S, r, 0.001f, rec, Ls, ps.rng, ph);
     else hit = scene_hit<F>(S, r, 0.001f, rec, ps.rng, Ls);
@@ -636,6 +679,17 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
         return true;
     }
     ps.depth++;
+    // Cornell walk: every lane here is glass or lambertian, and the first draw of either scatter -- the
+    // reflect test's, the light-or-cosine choice's -- is the stream's next output: made ONCE, by all of
+    // them together, instead of by each branch at its sliver of the wave (a PCG step and its output
+    // function, three 32-bit multiplies among them).  Each branch commits the state where it made the
+    // draw before, so every stream position is what it was.
+    PreDraw pd{0.0f, 0u};
+    if constexpr (kBox6Walk<F>) {
+        Pcg nx = ps.rng;
+        pd.v = randf(nx);
+        pd.state = nx.state;
+    }
     pr->o = rec.p;
     pr->time = r.time;
     pr->inside = 0;
@@ -658,7 +712,7 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     }
     if (M.kind == MRT_M_DIELECTRIC) {  // dielectric::scatter (material.h:121-175)
         BSTAT(5);
-        dielectric_scatter(M, r, rec.n, ps.rng, pr);
+        dielectric_scatter(M, r, rec.n, ps.rng, pr, kBox6Walk<F> ? &pd : nullptr);
         return false;
     }
     // lambertian / isotropic (material.h:48-74): the direction now, the pdfs after the ray exists
@@ -679,7 +733,16 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     // right here.
     v4f axq{0.0f, 0.0f, 0.0f, 0.0f};
     if constexpr (kBox6Walk<F>) axq = *(const MRT_LDS_AS v4f*)(uintptr_t)(Ls.axes + hid * (kHitAxisWords * 4u));
-    const bool light = ((F & FT_BIASED) && S.biased != MRT_NONE) && randf(ps.rng) < 0.5f;
+    bool light;
+    if constexpr (kBox6Walk<F>) {
+        light = false;
+        if ((F & FT_BIASED) && has_biased<F>(S, cw)) {  // (no biased list: no draw)
+            light = pd.v < 0.5f;
+            ps.rng.state = pd.state;
+        }
+    } else {
+        light = ((F & FT_BIASED) && S.biased != MRT_NONE) && randf(ps.rng) < 0.5f;
+    }
     Draws dr{0.0f, 0.0f, 2u};
     if (lamb && predraw_ok<F>(S, light)) {
         dr.v0 = randf(ps.rng);
@@ -688,7 +751,7 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     }
     BSTATC(7, light);
     if (light) {
-        pr->dir = biased_pdf_generate<F>(S, rec.p, r.time, ps.rng, dr);
+        pr->dir = biased_pdf_generate<F>(S, rec.p, r.time, ps.rng, dr, cw);
     } else if constexpr (kBox6Walk<F>) {
         if (lamb) {
             const f3 vec = random_cosine_direction_pre(dr.v0, dr.v1);
@@ -711,7 +774,7 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
 
 // the rest of a diffuse scatter once ps.r = make_ray(pr): mix_pdf value (main.cpp:84-102), level
 template <uint32_t F, uint32_t LK>
-MRT_DFN void finish_scatter(const DScene& S, PathState& ps, const LevStore<LK>& lev, const PendRay& pr) {
+MRT_DFN void finish_scatter(const DScene& S, PathState& ps, const LevStore<LK>& lev, const PendRay& pr, const CornellWords* cw = nullptr) {
     const Ray& sc = ps.r;
     float sval, spdf;
     if (pr.kind == 1u) {
@@ -726,17 +789,17 @@ MRT_DFN void finish_scatter(const DScene& S, PathState& ps, const LevStore<LK>& 
         spdf = 1.0f / (2.0f * PI_F);
     }
     float pdf_v = sval;
-    if ((F & FT_BIASED) && S.biased != MRT_NONE) {
+    if ((F & FT_BIASED) && has_biased<F>(S, cw)) {
         float bv;
-        if (kBox6Walk<F> && S.light_once) {
+        if (light_once<F>(S, cw)) {
             // the biased list is the walk's light: xz_rect::pdf_value from the ray's one light test
             // (ps.lt; the rect's words from op 3, the biased leaf's bit for bit)
-            const CornellRect d = cornell_load(const_ptr(S.prog)[3]);
+            const CornellRect& d = cw->light;
             const float f[6] = {__uint_as_float(d.b0), __uint_as_float(d.b1), __uint_as_float(d.b2), __uint_as_float(d.b3),
                                 __uint_as_float(d.k), __uint_as_float(d.ns)};
             bv = xz_pdf_of_hit(f, sc.d, !(ps.lt < 0.0f), ps.lt);
         } else {
-            bv = biased_pdf_value<F>(S, sc.o, sc.d, sc.time);
+            bv = biased_pdf_value<F>(cold_scene<F>(S), sc.o, sc.d, sc.time);
         }
         pdf_v = 0.5f * (bv + sval);
     }

@@ -603,6 +603,35 @@ template <typename... D>
 MRT_DFN void cornell_take(D&... d) {
     (cornell_take1(d), ...);
 }
+// The walk's scene words as state of the launch: the room's corners and mask (END op), the light's
+// rect (op 3), the box's frame and planes (ops 7, 8), the sphere (op 17) and the depth limit -- 29
+// words, constant for the launch.  The path loop loads them once before its first path and holds them
+// in scalar registers across the back edge (mrt_kernels.hip); read where they were used, they were five
+// scalar round trips in every iteration, each waited for at once.
+struct CornellWords {
+    CornellRoom room;  // (lo, hi, mask: the faces' materials come from the hit table)
+    CornellRect light; // (b0..b3, k, ns)
+    CornellBox box;
+    CornellSphere sph;
+    uint32_t max_bounces;
+    uint32_t flags;    // the launch's wave-uniform booleans as bits (kCw*), not one 64-bit mask each
+};
+// (every other kernel: no such state, a null pointer where a Cornell walk kernel hands its words down)
+struct NoCornellWords {};
+MRT_DFN const CornellWords* cornell_ptr(const CornellWords& c) { return &c; }
+MRT_DFN const CornellWords* cornell_ptr(const NoCornellWords&) { return nullptr; }
+// CornellWords::flags: the scene has a biased list; DScene::light_once; DScene::blist; per-path ray
+// counts are wanted (PathParams::path_rays).  Tested with a scalar bit compare where used
+// (cornell_words_hold keeps the test from being hoisted out of the path loop into a lane mask).
+enum : uint32_t { kCwBiased = 0, kCwLightOnce = 1, kCwBlist = 2, kCwPathRays = 3 };
+MRT_DFN bool cornell_flag(const CornellWords* cw, uint32_t bit) { return ((cw->flags >> bit) & 1u) != 0u; }
+MRT_DFN void cornell_take1(CornellRect& d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(d.b0), "+s"(d.b1), "+s"(d.b2), "+s"(d.b3), "+s"(d.k), "+s"(d.ns));
+#else
+    (void)d;
+#endif
+}
 // The light (op 3) is tested ONCE per ray, when the ray is made: its t with the walk's tmin and no
 // upper bound, kCornellMiss for a miss.  The walk then only compares it with the room's hit
 // (a rect test's compare and tie rule), and a scattered ray's xz_rect::pdf_value reads its hit
@@ -610,9 +639,8 @@ MRT_DFN void cornell_take(D&... d) {
 // the same rect a second time.
 static constexpr float kCornellTmin = 0.001f, kCornellMiss = -1.0f;  // (a hit's t is >= tmin > 0, or NaN)
 template <uint32_t F>
-MRT_DFN float cornell_light_t(const MRT_CONST_AS LinOp* prog, const Ray& r) {
+MRT_DFN float cornell_light_t(const CornellRect& d, const Ray& r) {
     static_assert(kSigs[SIG_CORNELL].op[3] == LOP_PRIM && kSigs[SIG_CORNELL].kind[3] == MRT_K_XZ, "Cornell shape: the light at op 3");
-    const CornellRect d = cornell_load(prog[3]);
     LinOp o;
     o.code = 0;  // (lin_prim_t reads the flags only under the exact contract's guards)
     o.f[0] = __uint_as_float(d.b0);
@@ -624,6 +652,32 @@ MRT_DFN float cornell_light_t(const MRT_CONST_AS LinOp* prog, const Ray& r) {
     float t;
     const bool h = lin_prim_t<F, MRT_K_XZ>(o, r, kCornellTmin, FLT_MAX_, &t);
     return h ? t : kCornellMiss;
+}
+// the launch's words, each group one batch of scalar loads taken at one point (cornell_take)
+MRT_DFN CornellWords cornell_words(const MRT_CONST_AS LinOp* prog, uint32_t max_bounces, uint32_t flags) {
+    constexpr const LinSig& G = kSigs[SIG_CORNELL];
+    static_assert(G.op[G.n - 1] == LOP_END, "the room is kept in the END op");
+    CornellWords cw{cornell_load_room(prog[G.n - 1]), cornell_load(prog[3]), cornell_load_box(prog[7], prog[8]),
+                    cornell_load_sphere(prog[17]), max_bounces, uniform_u32(flags)};
+    cornell_take_faces(cw.room);
+    cornell_take(cw.light, cw.box, cw.sph);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(cw.max_bounces), "+s"(cw.flags));
+#endif
+    return cw;
+}
+// At the top of every iteration of the path loop the words pass through empty asms IN PLACE (the
+// register allocator keeps each in its register: no instruction), so nothing computed from them is
+// loop-invariant to the compiler.  Without it an expression of scene words alone -- the sphere's
+// radius squared, the light's extents -- is hoisted out of the loop, leaves the block of its consumer,
+// and is no longer contracted into it (an fma): other bits than where the words were loaded at their
+// uses.  It also keeps the flag tests scalar bit compares at their uses.
+MRT_DFN void cornell_words_hold(CornellWords& cw) {
+    cornell_take_faces(cw.room);
+    cornell_take(cw.light, cw.box, cw.sph);
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(cw.max_bounces), "+s"(cw.flags));
+#endif
 }
 // 1 / radius of the sphere (op 17) as the record's divf takes it: wave-uniform, taken once per launch
 // by the path loop and held in an SGPR instead of a v_rcp_f32 per iteration
@@ -640,7 +694,7 @@ MRT_DFN float cornell_sphere_inv_rad(const MRT_CONST_AS LinOp* prog) {
 // *M: the hit's material, as S.mats[rec.mat] read it (rec.mat itself is not set: nothing reads it)
 // *hid: the hit's identity (the cosine scatter's index into the wave's basis axes, kHitAxisWords)
 template <uint32_t F>
-MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, float tmin, float lt, float inv_rad, uint32_t hits,
+MRT_DFN bool cornell_fast_hit(const CornellWords& cw, const Ray& r, float tmin, float lt, float inv_rad, uint32_t hits,
                               HitRec& rec, DMat* M, uint32_t* hid) {
     constexpr const LinSig& G = kSigs[SIG_CORNELL];
     static_assert(G.op[7] == LOP_INST && G.kind[7] == MRT_K_TRROTY && G.op[8] == LOP_LIST && G.skip[8] == 15 &&
@@ -649,10 +703,8 @@ MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, floa
     static_assert(!(F & FT_TEX), "the hit table keeps a material's constant colour only");
     CornellRec w{FLT_MAX_, kHitNone, 0.0f, 0u};
     // the room's walls as one slab test (ops 1, 2, 4, 5, 6; cornell_room_fill), then the light
-    // (op 3), the box and the sphere: their words in two batches of scalar loads
-    static_assert(G.op[G.n - 1] == LOP_END, "the room is kept in the END op");
-    CornellRoom dr = cornell_load_room(prog[G.n - 1]);
-    cornell_take_faces(dr);
+    // (op 3), the box and the sphere: their words are the launch's (CornellWords)
+    const CornellRoom& dr = cw.room;
     cornell_room<F>(dr, r, tmin, w);
     {  // the light: a rect test's outcome from the ray's one test (cornell_light_t, made with this tmin)
         (void)tmin;
@@ -660,9 +712,8 @@ MRT_DFN bool cornell_fast_hit(const MRT_CONST_AS LinOp* prog, const Ray& r, floa
         w.closest = h ? lt : w.closest;
         w.id = h ? kHitLight : w.id;
     }
-    CornellBox db = cornell_load_box(prog[7], prog[8]);
-    CornellSphere dsp = cornell_load_sphere(prog[17]);
-    cornell_take(db, dsp);
+    const CornellBox& db = cw.box;
+    const CornellSphere& dsp = cw.sph;
     // the box in its own frame: o' = R(o - offset), d' = R d, R = rotate_y's (s, c)
     const float s = __uint_as_float(db.s), c = __uint_as_float(db.c);
     const float off0 = __uint_as_float(db.o0), off1 = __uint_as_float(db.o1), off2 = __uint_as_float(db.o2);
@@ -753,11 +804,11 @@ static constexpr uint32_t kBox6Walk = (MRT_FAST_BOX && MRT_SIG_OF(F) == SIG_CORN
 // instead of S.mats[rec.mat]; the hit's identity)
 template <uint32_t F>
 MRT_DFN bool scene_hit_sig(const DScene& S, Ray& r, float tmin, HitRec& rec, const LStack& L, float lt = 0.0f, float inv_rad = 0.0f,
-                           DMat* M = nullptr, uint32_t* hid = nullptr) {
+                           DMat* M = nullptr, uint32_t* hid = nullptr, const CornellWords* cw = nullptr) {
     constexpr uint32_t SIG = MRT_SIG_OF(F);
     constexpr bool INST = (F & FT_INST) != 0;
     if constexpr (kBox6Walk<F>) {  // (the shape implies MRT_F_BOX6 on op 8: lin_sig_of)
-        return cornell_fast_hit<F>(const_ptr(S.prog), r, tmin, lt, inv_rad, L.hits, rec, M, hid);
+        return cornell_fast_hit<F>(*cw, r, tmin, lt, inv_rad, L.hits, rec, M, hid);
     } else {
     if (INST) lin_save_ray(L, r);
     const MRT_CONST_AS LinOp* prog = const_ptr(S.prog);
