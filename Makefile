@@ -18,7 +18,7 @@ OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
            $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
-           $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
+           $(OBJDIR)/mrt_temporal.o $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
 # (-fno-hip-fp32-correctly-rounded-divide-sqrt: f32 division by v_rcp_f32 + multiply instead of
@@ -84,6 +84,12 @@ $(OBJDIR)/mrt_adaptive.o: $(CSRC)/mrt_adaptive.hip include/mrt_adaptive.h $(HDRS
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# temporal reprojection, host and device from include/mrt_temporal.h, and the camera-record store:
+# no contraction on either side (HIPFLAGS, no fast flags); a translation unit of its own
+$(OBJDIR)/mrt_temporal.o: $(CSRC)/mrt_temporal.hip include/mrt_temporal.h include/mrt_denoise.h $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(HIPDEV) -c $< -o $@
@@ -116,7 +122,17 @@ tables-check: build/tables_check
 	MRT_ASSET_DIR=assets build/tables_check > build/tables_check.out
 	python3 tools/tables_digest.py --compare < build/tables_check.out
 
+# The host forms of mrt_make_camera and mrt_reproject stand-alone under the same sanitizers (host
+# code only, nothing preloaded; not part of `all`): tools/temporal_check.cpp
+TEMPORAL_CHECK_SRC = tools/temporal_check.cpp $(CSRC)/mrt_temporal.hip $(CSRC)/scene_builder.cpp $(CSRC)/mrt_common.cpp
+build/temporal_check: $(TEMPORAL_CHECK_SRC) include/mrt_temporal.h include/mrt_denoise.h $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) --offload-host-only -x hip -DMRT_TEMPORAL_HOST_ONLY=1 $(SANFLAGS) $(TEMPORAL_CHECK_SRC) -ldl -o $@
+
+temporal-check: build/temporal_check
+	build/temporal_check
+
 clean:
 	rm -rf build miniraytracer_amd/libmrt.so bin oracle/liboracle.so
 
-.PHONY: all clean tables-check
+.PHONY: all clean tables-check temporal-check

@@ -17,6 +17,10 @@
  *   mrt_lum_max_device/mrt_tonemap_device the same, on the device              main.cpp:421-442
  *   mrt_render_adaptive / mrt_moments     (new) draw()'s fixed sample loop, per pixel as long as its
  *                                         standard error asks                main.cpp:150-167
+ *   mrt_make_camera / mrt_scene_set_camera camera's constructor, for a scene that is already
+ *                                         uploaded                          camera.h:16-36
+ *   mrt_reproject                         (new) carries a frame's samples into the next frame of a
+ *                                         sequence; main() renders one still frame
  *
  * Threading: one host thread per device; calls on distinct scenes are thread-safe, calls on the
  * same scene handle are not reentrant.
@@ -309,6 +313,64 @@ typedef struct mrt_adaptive_params { uint32_t max_passes; float atol, rtol; } mr
 void mrt_default_adaptive_params(mrt_adaptive_params* p);
 mrt_status mrt_render_adaptive(mrt_scene* s, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out,
                                float* moments_out /* may be NULL */, uint64_t* rays_out, const volatile int* cancel);
+
+/* ---- camera and temporal accumulation ----------------------------------------------------------
+ * (an addition; the reference renders one still frame from the camera select_scene bakes in.)
+ *
+ * The camera.  mrt_camera (mrt_scene.h) holds the derived vectors the camera ctor computes
+ * (camera.h:16-36); mrt_make_camera is that arithmetic, the one definition the scene builders use
+ * too, so mrt_make_camera(mrt_scene_camera_params(blob)) equals the blob view's camera byte for byte.
+ * MRT_ERR_INVALID for a degenerate frame: a non-finite field, pos == lookat, up parallel to the view
+ * direction, vfov_deg outside (0, 180), aspect <= 0, focus_dist <= 0, aperture < 0. */
+typedef struct mrt_camera_params {
+    float pos[3], lookat[3], up[3];
+    float vfov_deg, aspect, aperture, focus_dist, time0, time1;
+} mrt_camera_params;
+mrt_status mrt_make_camera(const mrt_camera_params* p, mrt_camera* out);
+/* the parameters the scene's builder used (the blob keeps them) */
+mrt_status mrt_scene_camera_params(const mrt_scene_blob* blob, mrt_camera_params* out);
+/* Replace the camera of an uploaded scene; nothing else of the upload depends on it (the scene
+ * tables, the kernel variant and its tables do not read the camera), so no re-upload is needed.
+ * Both backends.  Blocks: waits for the scene's pending work (its last mrt_render_device, the fold
+ * included, and mrt_render_aux_device), then replaces the camera; renders and feature buffers made
+ * afterwards equal those of a scene uploaded with `cam` in its view bit for bit.
+ * MRT_ERR_INVALID: null, or a camera with a non-finite field. */
+mrt_status mrt_scene_set_camera(mrt_scene* s, const mrt_camera* cam);
+/* GPU backend only.  The same in stream order: a one-wave kernel enqueued on `stream` takes *cam by
+ * value (read during the call) and stores the record; nothing is synchronised and nothing is
+ * allocated (capturable: a replay sets the captured camera again).  Work enqueued on `stream` earlier
+ * sees the old camera, later work the new one.  The caller orders it against work on other streams
+ * -- that includes the context's own fold stream under MRT_RF_FOLD_ASYNC: call it after
+ * mrt_render_join(s, stream). */
+mrt_status mrt_scene_set_camera_device(mrt_scene* s, const mrt_camera* cam, void* stream);
+
+/* Temporal reprojection: the new history frame (accumulated rgb, history length N) from the current
+ * frame's colour and feature buffers (mrt_render_aux: normal = (n, coverage), albedo = (a, depth))
+ * under `cam`, and the previous history frame with the feature buffers and camera it was made with.
+ * Each fully covered pixel's world point (pinhole ray through the pixel centre, the mean depth) is
+ * projected into the previous camera; the four bilinear taps around it that agree in normal, depth
+ * and albedo give the history, which the current colour joins as sample N + 1 (N capped at
+ * max_history); a pixel without agreeing taps starts again from (c, 1).  The exact formulas and the
+ * operation order: include/mrt_temporal.h (one source for host and device: same bits).
+ * Whole row-major W*H float4 frames, row 0 = bottom; hist == NULL is the first frame (prev_normal,
+ * prev_albedo and prev_cam are not read): hist_out = (rgb.xyz, 1).  hist_out is a frame of its own
+ * (none of the inputs); the inputs are not written.
+ * Approximations: the lens is a pinhole at the camera's origin; time0 / time1 are ignored (moving
+ * spheres rely on the depth, normal and albedo tests); the depth is the feature buffers' mean t.
+ * Defaults (mrt_default_temporal_params; the CPU prototype's, measured again on the Cornell orbit,
+ * DESIGN.md): max_history 32, normal_min 0.9, depth_tol 0.02, albedo_tol 0.1, min_weight 0.25
+ * Valid: max_history >= 1; normal_min in [-1, 1]; depth_tol, albedo_tol > 0; min_weight in (0, 1];
+ * width, height in 1 .. 65536; finite cameras. */
+typedef struct mrt_temporal_params { float max_history, normal_min, depth_tol, albedo_tol, min_weight; } mrt_temporal_params;
+void mrt_default_temporal_params(mrt_temporal_params* p);
+mrt_status mrt_reproject(const float* rgb, const float* normal, const float* albedo, const mrt_camera* cam, const float* hist,
+                         const float* prev_normal, const float* prev_albedo, const mrt_camera* prev_cam, uint32_t width, uint32_t height,
+                         const mrt_temporal_params* p, float* hist_out);       /* host buffers */
+mrt_status mrt_reproject_device(const float* d_rgb, const float* d_normal, const float* d_albedo, const mrt_camera* cam, const float* d_hist,
+                                const float* d_prev_normal, const float* d_prev_albedo, const mrt_camera* prev_cam, uint32_t width,
+                                uint32_t height, const mrt_temporal_params* p, float* d_hist_out, void* stream);
+        /* GPU; device frames (16-byte aligned), host cameras and params (read during the call, passed
+           to the kernel by value); enqueued on `stream`, no sync, no allocation (capturable) */
 
 /* ---- multi-GPU: the framebuffer gather over RCCL (xGMI) ---------------------------------------
  * The reference's seam is main.cpp:347-382 (the worker threads over one work_queue) writing

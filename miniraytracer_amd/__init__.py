@@ -67,6 +67,13 @@ class Scene:
         check(lib().mrt_worker_seeds(self._h, n_threads, a.ctypes.data, b.ctypes.data), "mrt_worker_seeds")
         return [(int(x), int(y)) for x, y in zip(a, b)]
 
+    def camera_params(self):
+        """The mrt_camera_params the scene's builder used (position, look-at, up, vfov_deg, aspect,
+        aperture, focus_dist, time0, time1): make_camera(scene.camera_params()) is scene.view.camera."""
+        p = _lib.MrtCameraParams()
+        check(lib().mrt_scene_camera_params(self._h, C.byref(p)), "mrt_scene_camera_params")
+        return p
+
     def close(self):
         if self._h:
             lib().mrt_scene_blob_free(self._h)
@@ -199,6 +206,17 @@ class Renderer:
         check(lib().mrt_render_adaptive(self._h, C.byref(desc), C.byref(p), img.ctypes.data, mom.ctypes.data, C.byref(rays),
                                         C.byref(cancel) if cancel is not None else None), "mrt_render_adaptive")
         return img, mom, rays.value
+
+    def set_camera(self, cam, stream_ptr=None):
+        """Replace the scene's camera (an MrtCamera, e.g. make_camera(...)); nothing is uploaded again.
+        stream_ptr=None: the blocking form (both backends; waits for the scene's pending work).
+        Otherwise (GPU): enqueued on that HIP stream (0 = the null stream) -- renders enqueued on it
+        earlier see the old camera, later ones the new; capturable; the caller orders it against work on
+        other streams (after join() under RF_FOLD_ASYNC)."""
+        if stream_ptr is None:
+            check(lib().mrt_scene_set_camera(self._h, C.byref(cam)), "mrt_scene_set_camera")
+        else:
+            check(lib().mrt_scene_set_camera_device(self._h, C.byref(cam), C.c_void_p(stream_ptr)), "mrt_scene_set_camera_device")
 
     def join(self, stream_ptr=0):
         """Order a HIP stream after this context's last render_device (its fold runs on the context's
@@ -414,6 +432,76 @@ def moments_refine(moments, atol, rtol):
     out = np.zeros(m.shape[:-1], dtype=np.uint8)
     check(lib().mrt_moments_decide(m.ctypes.data, out.size, atol, rtol, out.ctypes.data, None), "mrt_moments_decide")
     return out.astype(bool)
+
+
+def make_camera(params=None, **kw):
+    """mrt_make_camera (include/mrt.h): the MrtCamera of camera parameters -- an MrtCameraParams (e.g.
+    scene.camera_params()), with fields overridden by keywords: pos, lookat, up (3 floats each),
+    vfov_deg, aspect, aperture, focus_dist, time0, time1.  Raises MrtError for a degenerate frame."""
+    p = _lib.MrtCameraParams()
+    if params is not None:
+        C.memmove(C.byref(p), C.byref(params), C.sizeof(p))
+    elif not {"pos", "lookat", "vfov_deg", "focus_dist"} <= set(kw):
+        raise ValueError("make_camera: without params, give at least pos, lookat, vfov_deg and focus_dist")
+    else:
+        p.up[:] = (0.0, 1.0, 0.0)
+        p.aspect, p.time0, p.time1 = 1.0, 0.0, 1.0
+    for k, v in kw.items():
+        if k in ("pos", "lookat", "up"):
+            getattr(p, k)[:] = [float(x) for x in v]
+        elif k in ("vfov_deg", "aspect", "aperture", "focus_dist", "time0", "time1"):
+            setattr(p, k, float(v))
+        else:
+            raise TypeError(f"make_camera: unknown parameter {k}")
+    cam = _lib.MrtCamera()
+    check(lib().mrt_make_camera(C.byref(p), C.byref(cam)), "mrt_make_camera")
+    return cam
+
+
+def default_temporal_params(**kw):
+    """mrt_temporal_params with the library's defaults (max_history, normal_min, depth_tol, albedo_tol,
+    min_weight), overridden where given."""
+    p = _lib.MrtTemporalParams()
+    lib().mrt_default_temporal_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(p._fields_):
+            raise TypeError(f"default_temporal_params: unknown parameter {k}")
+        setattr(p, k, v)
+    return p
+
+
+def reproject(img, normal, albedo, cam, hist=None, prev_normal=None, prev_albedo=None, prev_cam=None, params=None):
+    """Temporal reprojection on the host (include/mrt_temporal.h): the new history frame (H, W, 4) --
+    (accumulated rgb, history length) -- from the current colour and feature buffers under `cam` and
+    the previous history frame with the feature buffers and camera it was made with.  hist=None is
+    the first frame: (img.xyz, 1)."""
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    fr = [np.ascontiguousarray(a, dtype=np.float32) for a in (normal, albedo)]
+    if hist is not None:
+        if prev_normal is None or prev_albedo is None or prev_cam is None:
+            raise ValueError("reproject: a history frame needs prev_normal, prev_albedo and prev_cam")
+        fr += [np.ascontiguousarray(a, dtype=np.float32) for a in (hist, prev_normal, prev_albedo)]
+    if img.ndim != 3 or img.shape[2] != 4 or any(a.shape != img.shape for a in fr):
+        raise ValueError("reproject: every frame must be an (H, W, 4) array of one shape")
+    p = params if params is not None else default_temporal_params()
+    h, w = img.shape[:2]
+    out = np.zeros_like(img)
+    prev = [a.ctypes.data for a in fr[2:]] if hist is not None else [None, None, None]
+    check(lib().mrt_reproject(img.ctypes.data, fr[0].ctypes.data, fr[1].ctypes.data, C.byref(cam), *prev,
+                              C.byref(prev_cam) if hist is not None else None, w, h, C.byref(p), out.ctypes.data), "mrt_reproject")
+    return out
+
+
+def reproject_device(d_rgb_ptr, d_normal_ptr, d_albedo_ptr, cam, width, height, d_out_ptr, d_hist_ptr=0, d_prev_normal_ptr=0,
+                     d_prev_albedo_ptr=0, prev_cam=None, params=None, stream_ptr=0):
+    """The same on whole row-major device frames (W*H float4 each, torch data_ptr()s), enqueued on a
+    HIP stream: the new history frame lands in d_out (none of the inputs; they are not written).
+    d_hist_ptr=0 is the first frame."""
+    p = params if params is not None else default_temporal_params()
+    check(lib().mrt_reproject_device(C.c_void_p(d_rgb_ptr), C.c_void_p(d_normal_ptr), C.c_void_p(d_albedo_ptr), C.byref(cam),
+                                     C.c_void_p(d_hist_ptr or None), C.c_void_p(d_prev_normal_ptr or None), C.c_void_p(d_prev_albedo_ptr or None),
+                                     C.byref(prev_cam) if prev_cam is not None else None, width, height, C.byref(p), C.c_void_p(d_out_ptr),
+                                     C.c_void_p(stream_ptr)), "mrt_reproject_device")
 
 
 def tonemap_argb(img):

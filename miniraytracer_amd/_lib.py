@@ -85,7 +85,19 @@ class MrtAdaptiveParams(C.Structure):
     _fields_ = [("max_passes", C.c_uint32), ("atol", C.c_float), ("rtol", C.c_float)]
 
 
-MOMENTS_DEPTH = 16  # samples mrt_moments_kernel keeps in flight (mrt_adaptive.hip MRT_MOMENTS_DEPTH): its loop's threshold
+class MrtCameraParams(C.Structure):
+    """mrt_camera_params (include/mrt.h): what the camera's constructor takes (camera.h:16-36)."""
+    _fields_ = [("pos", C.c_float * 3), ("lookat", C.c_float * 3), ("up", C.c_float * 3), ("vfov_deg", C.c_float),
+                ("aspect", C.c_float), ("aperture", C.c_float), ("focus_dist", C.c_float), ("time0", C.c_float), ("time1", C.c_float)]
+
+
+class MrtTemporalParams(C.Structure):
+    """mrt_temporal_params (include/mrt.h): the history cap and the reprojection's acceptance tests."""
+    _fields_ = [("max_history", C.c_float), ("normal_min", C.c_float), ("depth_tol", C.c_float), ("albedo_tol", C.c_float),
+                ("min_weight", C.c_float)]
+
+
+MOMENTS_DEPTH = 16 # samples mrt_moments_kernel keeps in flight (mrt_adaptive.hip MRT_MOMENTS_DEPTH): its loop's threshold
 
 
 class MrtError(RuntimeError):
@@ -194,6 +206,22 @@ def lib():
     L.mrt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(MrtRenderDesc), C.POINTER(MrtAdaptiveParams), C.c_void_p, C.c_void_p,
                                       C.POINTER(C.c_uint64), C.c_void_p]
     L.mrt_render_adaptive.restype = st
+    L.mrt_make_camera.argtypes = [C.POINTER(MrtCameraParams), C.POINTER(MrtCamera)]
+    L.mrt_make_camera.restype = st
+    L.mrt_scene_camera_params.argtypes = [C.c_void_p, C.POINTER(MrtCameraParams)]
+    L.mrt_scene_camera_params.restype = st
+    L.mrt_scene_set_camera.argtypes = [C.c_void_p, C.POINTER(MrtCamera)]
+    L.mrt_scene_set_camera.restype = st
+    L.mrt_scene_set_camera_device.argtypes = [C.c_void_p, C.POINTER(MrtCamera), C.c_void_p]
+    L.mrt_scene_set_camera_device.restype = st
+    L.mrt_default_temporal_params.argtypes = [C.POINTER(MrtTemporalParams)]
+    L.mrt_default_temporal_params.restype = None
+    L.mrt_reproject.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MrtCamera), C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.POINTER(MrtCamera), C.c_uint32, C.c_uint32, C.POINTER(MrtTemporalParams), C.c_void_p]
+    L.mrt_reproject.restype = st
+    L.mrt_reproject_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MrtCamera), C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(MrtCamera), C.c_uint32, C.c_uint32, C.POINTER(MrtTemporalParams), C.c_void_p, C.c_void_p]
+    L.mrt_reproject_device.restype = st
     _lib = L
     return L
 
@@ -216,4 +244,6 @@ EXPORTS = [
     "mrt_gather_shard_pixels", "mrt_gather_frame", "mrt_render_gather",
     "mrt_render_aux", "mrt_render_aux_device", "mrt_default_denoise_params", "mrt_denoise", "mrt_denoise_device",
     "mrt_moments", "mrt_moments_device", "mrt_moments_decide", "mrt_default_adaptive_params", "mrt_render_adaptive",
+    "mrt_make_camera", "mrt_scene_camera_params", "mrt_scene_set_camera", "mrt_scene_set_camera_device",
+    "mrt_default_temporal_params", "mrt_reproject", "mrt_reproject_device",
 ]

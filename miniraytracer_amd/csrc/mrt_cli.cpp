@@ -24,8 +24,15 @@
 // A line after "Trace:" reports the mean samples per pixel and the pixels refined per pass.  It
 // composes with -denoise, -aux, -backend cpu and -gpus N over the host assembly (every decision is
 // per pixel, so each rank refines its own); the RCCL gather does not carry adaptive frames.
+// -lookfrom x y z, -lookat x y z, -vfov D, -aperture A, -focus F replace the scene's camera (each
+// defaults to the scene's own parameter: mrt_scene_camera_params, mrt_make_camera,
+// mrt_scene_set_camera).  -frames N [-orbit DEG] renders a sequence into NAME_000.ext ...: frame k
+// turns lookfrom about the vertical axis through lookat by k * DEG and uses the seed
+// splitmix64(seed + k); -temporal accumulates the frames (mrt_reproject, feature buffers at
+// min(spp, 16) samples); -denoise N then filters what is written, never the history.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +46,138 @@
 static int fail(const char* what, mrt_status s) {
     fprintf(stderr, "%s: %s (%s)\n", what, mrt_strerror(s), mrt_last_error());
     return 1;
+}
+
+// -o: .ppm = Drago tone map (main.cpp:416-444), anything else = linear PFM; W*H float4, row 0 = bottom
+static int write_image(const char* path, const std::vector<float>& img, uint32_t w, uint32_t h) {
+    std::string o = path;
+    FILE* f = fopen(path, "wb");
+    if (!f) return fail("open output", MRT_ERR_IO);
+    if (o.size() > 4 && o.substr(o.size() - 4) == ".ppm") {
+        std::vector<uint32_t> argb((size_t)w * h);
+        mrt_tonemap_argb(img.data(), w, h, argb.data());
+        fprintf(f, "P6\n%u %u\n255\n", w, h);
+        for (int y = (int)h - 1; y >= 0; y--)  // display is flipped (platform_linux.cpp:84)
+            for (uint32_t x = 0; x < w; x++) {
+                uint32_t c = argb[(size_t)y * w + x];
+                unsigned char px[3] = {(unsigned char)(c >> 16), (unsigned char)(c >> 8), (unsigned char)c};
+                fwrite(px, 1, 3, f);
+            }
+    } else {
+        fprintf(f, "PF\n%u %u\n-1.0\n", w, h);
+        for (size_t i = 0; i < (size_t)w * h; i++) fwrite(&img[i * 4], 4, 3, f);
+    }
+    fclose(f);
+    return 0;
+}
+
+static uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// one job per rank on its own host thread, as the single-frame path runs them
+template <typename Fn>
+static mrt_status on_ranks(int world, Fn fn) {
+    std::vector<mrt_status> sts(world, MRT_OK);
+    std::vector<std::thread> th;
+    for (int r = 0; r < world; r++) th.emplace_back([&, r] { sts[r] = fn(r); });
+    for (auto& t : th) t.join();
+    for (mrt_status s : sts)
+        if (s) return s;
+    return MRT_OK;
+}
+
+// -frames N [-orbit DEG] [-temporal] [-denoise N]: frame k renders from the camera `cp` with its
+// position turned about the vertical axis through its look-at point by k * DEG, under the seed
+// splitmix64(seed + k), into NAME_00k.ext.  -temporal accumulates the frames through mrt_reproject
+// (feature buffers at min(spp, 16) samples, the library's default parameters); -denoise filters the
+// frame that is written, never the history.  Each rank renders its own pixels of the shared host
+// frame (the host assembly), on either backend.
+static int run_sequence(const mrt_params& p, std::vector<mrt_scene*>& scenes, std::vector<mrt_render_desc>& descs, const mrt_camera_params& cp,
+                        int frames, double orbit_deg, bool temporal, int denoise, const char* out) {
+    const int world = (int)scenes.size();
+    const uint32_t W = p.buffer_width, H = p.buffer_height;
+    const size_t npx = (size_t)W * H;
+    const bool guides = temporal || denoise >= 0;
+    std::vector<float> img(npx * 4), nrm(guides ? npx * 4 : 0), alb(guides ? npx * 4 : 0);
+    std::vector<float> pnrm, palb, hist, hist_new(temporal ? npx * 4 : 0), shown;
+    mrt_camera pcam{};
+    mrt_temporal_params tp;
+    mrt_default_temporal_params(&tp);
+    const uint64_t seed0 = descs[0].seed;
+    std::string stem = out ? out : "", ext;
+    const size_t dot = stem.rfind('.');
+    if (dot != std::string::npos && stem.find('/', dot) == std::string::npos) {
+        ext = stem.substr(dot);
+        stem.resize(dot);
+    }
+    for (int k = 0; k < frames; k++) {
+        mrt_camera_params ck = cp;
+        const double a = (double)k * orbit_deg * 3.14159265358979323846 / 180.0;
+        const double dx = (double)cp.pos[0] - (double)cp.lookat[0], dz = (double)cp.pos[2] - (double)cp.lookat[2];
+        ck.pos[0] = (float)((double)cp.lookat[0] + dx * cos(a) + dz * sin(a));
+        ck.pos[2] = (float)((double)cp.lookat[2] - dx * sin(a) + dz * cos(a));
+        mrt_camera cam;
+        mrt_status st = mrt_make_camera(&ck, &cam);
+        if (st) return fail("make_camera", st);
+        std::fill(img.begin(), img.end(), 0.0f);
+        std::vector<uint64_t> rays(world, 0);
+        auto t0 = std::chrono::steady_clock::now();
+        st = on_ranks(world, [&](int r) {
+            if (mrt_status s = mrt_scene_set_camera(scenes[r], &cam)) return s;
+            descs[r].seed = splitmix64(seed0 + (uint64_t)k);
+            return mrt_render(scenes[r], &descs[r], img.data(), &rays[r], nullptr);
+        });
+        if (st) return fail("render", st);
+        const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        uint64_t total = 0;
+        for (uint64_t x : rays) total += x;
+        if (guides) {
+            std::fill(nrm.begin(), nrm.end(), 0.0f);
+            std::fill(alb.begin(), alb.end(), 0.0f);
+            st = on_ranks(world, [&](int r) {
+                mrt_render_desc ad = descs[r];
+                ad.sqrt_samples = std::min(ad.sqrt_samples, 4u);
+                ad.flags = 0;
+                return mrt_render_aux(scenes[r], &ad, nrm.data(), alb.data());
+            });
+            if (st) return fail("render_aux", st);
+        }
+        const std::vector<float>* frame = &img;
+        size_t kept = 0;
+        if (temporal) {
+            st = mrt_reproject(img.data(), nrm.data(), alb.data(), &cam, k ? hist.data() : nullptr, k ? pnrm.data() : nullptr, k ? palb.data() : nullptr,
+                               k ? &pcam : nullptr, W, H, &tp, hist_new.data());
+            if (st) return fail("reproject", st);
+            hist.swap(hist_new);
+            if (hist_new.size() != hist.size()) hist_new.resize(hist.size());
+            pnrm = nrm;
+            palb = alb;
+            pcam = cam;
+            for (size_t i = 0; i < npx; i++) kept += hist[i * 4 + 3] > 1.0f;
+            frame = &hist;
+        }
+        if (denoise >= 0) {  // for output only: the history stays unfiltered
+            mrt_denoise_params dp;
+            mrt_default_denoise_params(&dp);
+            dp.iterations = (uint32_t)denoise;
+            shown.resize(npx * 4);
+            if ((st = mrt_denoise(frame->data(), nrm.data(), alb.data(), W, H, &dp, shown.data()))) return fail("denoise", st);
+            frame = &shown;
+        }
+        printf("frame %03d: %.2f deg, %.3fs, rays %llu", k, (double)k * orbit_deg, secs, (unsigned long long)total);
+        if (temporal) printf(", history at %.1f%% of the pixels", 100.0 * (double)kept / (double)npx);
+        printf("\n");
+        if (out) {
+            char num[16];
+            snprintf(num, sizeof num, "_%03d", k);
+            if (write_image((stem + num + ext).c_str(), *frame, W, H)) return 1;
+        }
+    }
+    return 0;
 }
 
 int main(int argc, char** argv) {
@@ -61,6 +200,37 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "-gather")) gather = argv[i + 1];
         if (!strcmp(argv[i], "-aux")) aux = argv[i + 1];
         if (!strcmp(argv[i], "-denoise")) denoise = atoi(argv[i + 1]);
+    }
+    // camera and sequence flags: each camera flag defaults to the scene's own parameter
+    const char* lookfrom = nullptr;
+    const char* lookat = nullptr;
+    const char *vfov = nullptr, *aperture = nullptr, *focus = nullptr, *frames_s = nullptr;
+    int lookfrom_i = 0, lookat_i = 0;
+    double orbit_deg = 0.0;
+    bool temporal = false, have_orbit = false;
+    for (int i = 1; i < argc; i++) {
+        const bool v1 = i + 1 < argc, v3 = i + 3 < argc;
+        if (!strcmp(argv[i], "-temporal")) temporal = true;
+        if (!strcmp(argv[i], "-lookfrom") && v3) lookfrom = argv[lookfrom_i = i + 1];
+        if (!strcmp(argv[i], "-lookat") && v3) lookat = argv[lookat_i = i + 1];
+        if (!strcmp(argv[i], "-vfov") && v1) vfov = argv[i + 1];
+        if (!strcmp(argv[i], "-aperture") && v1) aperture = argv[i + 1];
+        if (!strcmp(argv[i], "-focus") && v1) focus = argv[i + 1];
+        if (!strcmp(argv[i], "-frames") && v1) frames_s = argv[i + 1];
+        if (!strcmp(argv[i], "-orbit") && v1) {
+            orbit_deg = strtod(argv[i + 1], nullptr);
+            have_orbit = true;
+        }
+    }
+    const bool have_cam = lookfrom || lookat || vfov || aperture || focus;
+    const int frames = frames_s ? atoi(frames_s) : 0;
+    if (frames_s && (frames < 1 || frames > 999)) {
+        fprintf(stderr, "-frames: 1 to 999 frames\n");
+        return 1;
+    }
+    if ((temporal || have_orbit) && !frames_s) {
+        fprintf(stderr, "-temporal / -orbit: need -frames N\n");
+        return 1;
     }
     if (denoise > 16) {
         fprintf(stderr, "-denoise: 0 to 16 passes\n");
@@ -142,6 +312,33 @@ int main(int argc, char** argv) {
         fprintf(stderr, "-gather rccl: needs the GPU backend and a GPU per rank (%d ranks, %d GPUs)\n", world, ndev);
         return 1;
     }
+    // the camera flags replace the uploaded scenes' camera (nothing is built or uploaded again)
+    mrt_camera_params cp;
+    if ((st = mrt_scene_camera_params(blob, &cp))) return fail("scene_camera_params", st);
+    if (have_cam) {
+        for (int k = 0; k < 3; k++) {
+            if (lookfrom) cp.pos[k] = strtof(argv[lookfrom_i + k], nullptr);
+            if (lookat) cp.lookat[k] = strtof(argv[lookat_i + k], nullptr);
+        }
+        if (vfov) cp.vfov_deg = strtof(vfov, nullptr);
+        if (aperture) cp.aperture = strtof(aperture, nullptr);
+        if (focus) cp.focus_dist = strtof(focus, nullptr);
+        mrt_camera cam;
+        if ((st = mrt_make_camera(&cp, &cam))) return fail("make_camera", st);
+        for (int r = 0; r < world; r++)
+            if ((st = mrt_scene_set_camera(scenes[r], &cam))) return fail("scene_set_camera", st);
+    }
+    if (frames_s) {
+        if (have_adaptive || aux || (gather && !strcmp(gather, "rccl"))) {
+            fprintf(stderr, "-frames: a sequence renders over the host assembly, without -adaptive, -aux or -gather rccl\n");
+            return 1;
+        }
+        const int rc = run_sequence(p, scenes, descs, cp, frames, orbit_deg, temporal, denoise, out);
+        for (auto* s : scenes) mrt_scene_free(s);
+        mrt_scene_blob_free(blob);
+        return rc;
+    }
+
     std::vector<mrt_comm*> comms(world, nullptr);
     if (use_rccl) {
         std::vector<int> devs(world);
@@ -247,26 +444,7 @@ int main(int argc, char** argv) {
         }
     }
 
-    if (out) {
-        std::string o = out;
-        FILE* f = fopen(out, "wb");
-        if (!f) return fail("open output", MRT_ERR_IO);
-        if (o.size() > 4 && o.substr(o.size() - 4) == ".ppm") {
-            std::vector<uint32_t> argb((size_t)p.buffer_width * p.buffer_height);
-            mrt_tonemap_argb(img.data(), p.buffer_width, p.buffer_height, argb.data());
-            fprintf(f, "P6\n%u %u\n255\n", p.buffer_width, p.buffer_height);
-            for (int y = (int)p.buffer_height - 1; y >= 0; y--)  // display is flipped (platform_linux.cpp:84)
-                for (uint32_t x = 0; x < p.buffer_width; x++) {
-                    uint32_t c = argb[(size_t)y * p.buffer_width + x];
-                    unsigned char px[3] = {(unsigned char)(c >> 16), (unsigned char)(c >> 8), (unsigned char)c};
-                    fwrite(px, 1, 3, f);
-                }
-        } else {
-            fprintf(f, "PF\n%u %u\n-1.0\n", p.buffer_width, p.buffer_height);
-            for (size_t i = 0; i < (size_t)p.buffer_width * p.buffer_height; i++) fwrite(&img[i * 4], 4, 3, f);
-        }
-        fclose(f);
-    }
+    if (out && write_image(out, img, p.buffer_width, p.buffer_height)) return 1;
     for (auto* c : comms) mrt_comm_free(c);
     for (auto* s : scenes) mrt_scene_free(s);
     mrt_scene_blob_free(blob);

@@ -7,6 +7,8 @@ struct mrt_cpu_scene;
 mrt_status mrt_cpu_scene_create(const mrt_scene_view* v, mrt_cpu_scene** out);
 void mrt_cpu_scene_free(mrt_cpu_scene* c);
 uint32_t mrt_cpu_scene_features(const mrt_cpu_scene* c);
+// mrt_scene_set_camera: later renders and feature buffers start their paths from *cam
+void mrt_cpu_set_camera(mrt_cpu_scene* c, const mrt_camera* cam);
 mrt_status mrt_cpu_render(mrt_cpu_scene* c, const mrt_render_desc* d, float* rgb_out, uint64_t* rays_out, const volatile int* cancel);
 // first-hit feature buffers (mrt_render_aux): host W*H*4 each, owned pixels only
 mrt_status mrt_cpu_render_aux(mrt_cpu_scene* c, const mrt_render_desc* d, float* normal_out, float* albedo_out);

@@ -142,6 +142,13 @@ void mrt_cpu_scene_free(mrt_cpu_scene* c) { delete c; }
 
 uint32_t mrt_cpu_scene_features(const mrt_cpu_scene* c) { return c->feats; }
 
+// the record behind S.camp (what camera_ray reads) and the copy in S; every render call has
+// returned by now (they block), so no worker reads either
+void mrt_cpu_set_camera(mrt_cpu_scene* c, const mrt_camera* cam) {
+    c->cam = *cam;
+    c->S.cam = *cam;
+}
+
 // one worker's stacks: the per-lane LDS stacks of the GPU walk, one lane wide (lane 0, the same
 // [slot][word][lane] indexing with a 64-word stride)
 struct Stacks {

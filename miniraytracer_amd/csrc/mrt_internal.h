@@ -27,3 +27,7 @@ std::vector<mrt_tile> mrt_internal_render_tiles(const mrt_render_desc* d);
 mrt_status mrt_internal_check_pixels(const mrt_render_desc* d);
 // the HIP device of a GPU-backend scene (MRT_DEVICE_CPU for the CPU backend)
 int mrt_internal_scene_device(const mrt_scene* s);
+// GPU: enqueue on `stream` (a hipStream_t) the one-wave kernel that stores *cam (taken by value at
+// the call) to the 16-byte aligned device record d_record and, when not NULL, to the 4-byte aligned
+// device copy d_words; nothing is synchronised or allocated (mrt_temporal.hip)
+mrt_status mrt_internal_camera_store(const mrt_camera* cam, void* d_record, void* d_words, void* stream);

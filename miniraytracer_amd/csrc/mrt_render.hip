@@ -15,6 +15,8 @@
 #include <mutex>
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <memory>
 #include <cstring>
 #include <string>
@@ -1251,6 +1253,42 @@ extern "C" mrt_status mrt_render_join(mrt_scene* s, void* stream) {
     if (!s->ev_done) return MRT_OK;  // no render yet
     HIPCHK(hipSetDevice(s->device));
     HIPCHK(hipStreamWaitEvent((hipStream_t)stream, s->ev_done, 0));
+    return MRT_OK;
+}
+
+// ---- the camera of an uploaded scene (include/mrt.h "camera and temporal accumulation") ----
+// Every kernel reads the camera through DScene::camp at each path start (mrt_shade.h camera_ray);
+// DScene::cam, the copy inside the struct (the host's s->S, handed to every launch by value, and the
+// uploaded d_S), is read by no kernel and is kept equal to it.  Nothing else of an upload depends on
+// the camera: the scene tables, the variant choice and the Cornell hit table do not read it.
+static mrt_status camera_check(const char* who, const mrt_scene* s, const mrt_camera* cam) {
+    if (!s || !cam) return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": null").c_str());
+    const float* f = (const float*)cam;
+    for (size_t i = 0; i < sizeof(mrt_camera) / 4; i++)
+        if (!std::isfinite(f[i])) return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": a camera with a non-finite field").c_str());
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_scene_set_camera(mrt_scene* s, const mrt_camera* cam) {
+    if (mrt_status st = camera_check("mrt_scene_set_camera", s, cam)) return st;
+    if (s->cpu) {
+        mrt_cpu_set_camera(s->cpu, cam);
+        return MRT_OK;
+    }
+    HIPCHK(hipSetDevice(s->device));
+    if (mrt_status st = quiesce(s)) return st;  // the context's last render (its fold included) and feature buffers
+    HIPCHK(hipMemcpy(const_cast<mrt_camera*>(s->S.camp), cam, sizeof(mrt_camera), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy((char*)s->d_S + offsetof(DScene, cam), cam, sizeof(mrt_camera), hipMemcpyHostToDevice));
+    s->S.cam = *cam;
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_scene_set_camera_device(mrt_scene* s, const mrt_camera* cam, void* stream) {
+    MRT_GPU_ONLY(s, "mrt_scene_set_camera_device");
+    if (mrt_status st = camera_check("mrt_scene_set_camera_device", s, cam)) return st;
+    HIPCHK(hipSetDevice(s->device));
+    if (mrt_status st = mrt_internal_camera_store(cam, const_cast<mrt_camera*>(s->S.camp), (char*)s->d_S + offsetof(DScene, cam), stream)) return st;
+    s->S.cam = *cam;
     return MRT_OK;
 }
 

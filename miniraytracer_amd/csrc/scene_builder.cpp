@@ -506,35 +506,38 @@ struct Builder {
     }
 };
 
-// camera ctor (camera.h:16-36)
-static mrt_camera make_camera(V3 pos, V3 lookat, V3 up, float vfov, float aspect, float aperture, float focus_dist, float t0, float t1) {
-    mrt_camera c{};
-    c.time0 = t0;
-    c.time1 = t1;
-    float theta = rad(vfov);
-    float height = 2.0f * tan_(theta / 2);
-    float width = aspect * height;
-    V3 w = normalize(pos - lookat);
-    V3 u = normalize(cross(up, w));
-    V3 v = cross(w, u);
-    c.lens_radius = aperture / 2.0f;
-    V3 horz = (focus_dist * width) * u;
-    V3 vert = (focus_dist * height) * v;
-    V3 llc = ((pos - 0.5f * horz) - 0.5f * vert) - focus_dist * w;
-    auto put = [](float* d, V3 s) { d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = 0; };
-    put(c.origin, pos); put(c.u, u); put(c.v, v); put(c.w, w);
-    put(c.llcorner, llc); put(c.horz, horz); put(c.vert, vert);
-    return c;
+// a scene's camera: the parameters its builder chose and the record derived from them
+struct BuiltCam {
+    mrt_camera_params par{};
+    mrt_camera cam{};
+};
+
+// the builders' camera: their parameters through mrt_make_camera (below), the one definition of
+// the camera ctor's arithmetic
+static BuiltCam make_camera(V3 pos, V3 lookat, V3 up, float vfov, float aspect, float aperture, float focus_dist, float t0, float t1) {
+    BuiltCam b;
+    mrt_camera_params& p = b.par;
+    p.pos[0] = pos.x; p.pos[1] = pos.y; p.pos[2] = pos.z;
+    p.lookat[0] = lookat.x; p.lookat[1] = lookat.y; p.lookat[2] = lookat.z;
+    p.up[0] = up.x; p.up[1] = up.y; p.up[2] = up.z;
+    p.vfov_deg = vfov;
+    p.aspect = aspect;
+    p.aperture = aperture;
+    p.focus_dist = focus_dist;
+    p.time0 = t0;
+    p.time1 = t1;
+    (void)mrt_make_camera(&p, &b.cam);  // (the reference scenes' frames are not degenerate)
+    return b;
 }
 
 struct BuiltScene {
     HObj* objects = nullptr;
     HObj* biased = nullptr;
-    mrt_camera cam{};
+    BuiltCam cam{};
 };
 
 static const V3 SPHERE_CAM_POS{11, 2.2f, 2.5f}, SPHERE_LOOKAT{2.8f, 0.5f, 1.2f}, UP{0, 1, 0};
-static mrt_camera sphere_cam(float aspect) {
+static BuiltCam sphere_cam(float aspect) {
     return make_camera(SPHERE_CAM_POS, SPHERE_LOOKAT, UP, 27.0f, aspect, 0.09f, length(SPHERE_CAM_POS - SPHERE_LOOKAT), 0.0f, 1.0f);
 }
 
@@ -894,7 +897,50 @@ struct mrt_scene_blob {
     float ranvec[256 * 4];
     int32_t perm[3 * 256];
     Pcg main_rng;  // main()'s T_rng after select_scene: the worker seeds come from it (main.cpp:357-361)
+    mrt_camera_params cam_params;  // what the scene's builder gave make_camera (mrt_scene_camera_params)
 };
+
+// camera ctor (camera.h:16-36): the derived vectors exactly as the constructor computes them
+extern "C" mrt_status mrt_make_camera(const mrt_camera_params* p, mrt_camera* out) {
+    if (!p || !out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_make_camera: null");
+    const float* f = p->pos;  // the struct is fifteen floats
+    static_assert(sizeof(mrt_camera_params) == 15 * sizeof(float), "mrt_camera_params is fifteen floats");
+    for (int i = 0; i < 15; i++)
+        if (!std::isfinite(f[i])) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_make_camera: a non-finite field");
+    if (!(p->vfov_deg > 0.0f && p->vfov_deg < 180.0f) || !(p->aspect > 0.0f) || !(p->focus_dist > 0.0f) || !(p->aperture >= 0.0f))
+        return mrt_internal_fail(MRT_ERR_INVALID, "mrt_make_camera: vfov in (0, 180), aspect and focus_dist > 0, aperture >= 0");
+    const V3 pos{p->pos[0], p->pos[1], p->pos[2]}, lookat{p->lookat[0], p->lookat[1], p->lookat[2]}, up{p->up[0], p->up[1], p->up[2]};
+    const float vfov = p->vfov_deg, aspect = p->aspect, aperture = p->aperture, focus_dist = p->focus_dist;
+    if (!(sdot(pos - lookat) > 0.0f)) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_make_camera: pos == lookat");
+    mrt_camera c{};
+    c.time0 = p->time0;
+    c.time1 = p->time1;
+    float theta = rad(vfov);
+    float height = 2.0f * tan_(theta / 2);
+    float width = aspect * height;
+    V3 w = normalize(pos - lookat);
+    if (!(sdot(cross(up, w)) > 0.0f)) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_make_camera: up is parallel to the view direction");
+    V3 u = normalize(cross(up, w));
+    V3 v = cross(w, u);
+    c.lens_radius = aperture / 2.0f;
+    V3 horz = (focus_dist * width) * u;
+    V3 vert = (focus_dist * height) * v;
+    V3 llc = ((pos - 0.5f * horz) - 0.5f * vert) - focus_dist * w;
+    auto put = [](float* d, V3 s) { d[0] = s.x; d[1] = s.y; d[2] = s.z; d[3] = 0; };
+    put(c.origin, pos); put(c.u, u); put(c.v, v); put(c.w, w);
+    put(c.llcorner, llc); put(c.horz, horz); put(c.vert, vert);
+    const float* g = c.origin;
+    for (size_t i = 0; i < sizeof c / sizeof(float); i++)
+        if (!std::isfinite(g[i])) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_make_camera: the frame overflows");
+    *out = c;
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_scene_camera_params(const mrt_scene_blob* blob, mrt_camera_params* out) {
+    if (!blob || !out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_scene_camera_params: null");
+    *out = blob->cam_params;
+    return MRT_OK;
+}
 
 static std::string default_asset_dir() {
     const char* e = getenv("MRT_ASSET_DIR");
@@ -936,7 +982,8 @@ extern "C" mrt_status mrt_select_scene(uint32_t scene, float aspect, const char*
     v.root = root;
     v.biased = biased;
     v.sky = scene < 5 ? 1u : 0u;  // main.cpp:110 (scene 9 renders as a Cornell scene)
-    v.camera = S.cam;
+    v.camera = S.cam.cam;
+    b->cam_params = S.cam.par;
     v.nodes = b->flat.nodes.data(); v.n_nodes = (uint32_t)b->flat.nodes.size();
     v.children = b->flat.children.data(); v.n_children = (uint32_t)b->flat.children.size();
     v.mesh_nodes = b->flat.mesh_nodes.data(); v.n_mesh_nodes = (uint32_t)b->flat.mesh_nodes.size();
