@@ -214,8 +214,9 @@ typedef struct mrt_kernel_info {
     /* handed_over: paths the fast-arithmetic kernels listed for the exact arithmetic since the
        scene's upload (rounding-critical light samples); handover_lost: listed
        paths beyond a launch's list capacity (they keep their fast radiance; 0 in every BASELINE
-       config).  Reading them waits for the scene's last render (its fold included).  pad: 0 */
-    uint32_t pad;
+       config).  Reading them waits for the scene's last render (its fold included).  n_cu: the compute
+       units of the scene's device, which the grid is a multiple of (0 on the CPU backend) */
+    uint32_t n_cu;
     uint64_t handed_over;
     uint64_t handover_lost;
 } mrt_kernel_info;

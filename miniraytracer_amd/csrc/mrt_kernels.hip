@@ -62,7 +62,10 @@ using namespace mrtd;
 #define MRT_WPE_WIDE (MRT_FAST ? 6 : 4)
 #endif
 #ifndef MRT_WPE_LIN
-#define MRT_WPE_LIN (MRT_FWD_FOLD ? 7 : 6)  // forward fold: no LDS levels, 72 VGPRs (C2 +1%)
+// forward fold: no LDS levels; 8 since the Cornell walk stores a path's radiance where it ends: 64 VGPRs,
+// and the 80 scalar registers a wave may hold for eight to fit a SIMD (7 before, 68 VGPRs; without the
+// attribute the kernel allocates 94 scalar registers, which run as seven waves on a grid sized for eight)
+#define MRT_WPE_LIN (MRT_FWD_FOLD ? 8 : 6)
 #endif
 #ifndef MRT_WPE_MESH
 #define MRT_WPE_MESH 7
@@ -261,7 +264,12 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     // one-wave group at LDS address 0, a constant)
     constexpr uint32_t hit_words = kBox6Walk<F> ? kHitLdsBytes / 4u : 0u;
     const uint32_t words = (P.lds_frames * 2 + P.lds_rays * 11 + P.lds_mesh + P.lds_save + LK * 4 + PathQ<F>::words) * 64 + hit_words;
-    uint32_t* wb = lds + wave * words + hit_words;
+    // A Cornell walk kernel's queue of path starts (with the claim state and the basis axes in its last
+    // row) comes straight behind the hit table, in front of the stacks and fold levels, whose sizes are
+    // launch parameters: in a one-wave group every queue address is then a constant of the kernel, not
+    // a scalar register held across the path loop (two of the 80 that eight waves per SIMD leave).
+    constexpr uint32_t q_front = kBox6Walk<F> ? PathQ<F>::words * 64u : 0u;
+    uint32_t* wb = lds + wave * words + hit_words + q_front;
     uint32_t* const wmesh = wb + P.lds_frames * 128 + P.lds_rays * 704;
     float4* tree = nullptr;
     if constexpr (TreeOf<F>::on) {
@@ -275,14 +283,18 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                     TreeOf<F>::on ? P.tree_n : 0u,
                     !kBox6Walk<F> ? 0u
                     : TreeOf<F>::wg == 64u ? (uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)lds  // (one wave: its slice is the group's)
-                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(wb - hit_words)),
+                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(wb - q_front - hit_words)),
                     // (the basis axes of the table's normals: in the claim row of the queue below, mrt_sig.h kHitAxisWord0)
                     !kBox6Walk<F> ? 0u
+                    : TreeOf<F>::wg == 64u ? (uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(lds + hit_words + 12u * 64u + kHitAxisWord0)
                     : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(
-                          wmesh + (P.lds_mesh + P.lds_save + LK * 4 + 12u) * 64 + kHitAxisWord0))};
+                          wb - q_front + 12u * 64u + kHitAxisWord0))};
     static_assert(!kBox6Walk<F> || PathQ<F>::on, "the Cornell walk's basis axes live in the queue's claim row");
     // the wave's queue of path starts ([word][entry], PathQ): after the fold levels
-    float* const Lq = (float*)(wmesh + (P.lds_mesh + P.lds_save + LK * 4) * 64);
+    // (Cornell walk: in front of the stacks, see q_front)
+    float* const Lq = !kBox6Walk<F>          ? (float*)(wmesh + (P.lds_mesh + P.lds_save + LK * 4) * 64)
+                      : TreeOf<F>::wg == 64u ? (float*)(lds + hit_words)
+                                             : (float*)(wb - q_front);
     const DScene& S = P.sc;
     const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const LevStore<LK> lev{(MRT_GLOBAL_AS v4f*)P.lev, P.lev_rows, (uint32_t)slot,
@@ -324,7 +336,8 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     uint32_t part_tries = 0;                 // partitions found handed out
     // the partitions a wave visits after its own: every one (step odd, coprime with 8); with
     // MRT_STEAL_SPREAD the waves of one partition leave it in four directions instead of one
-    const uint32_t steal_step = MRT_STEAL_SPREAD ? 1u + 2u * ((blockIdx.x / MRT_NPART) & 3u) : 1u;
+    // (a Cornell walk kernel keeps it in the claim row between claims, with the state below)
+    uint32_t steal_step = MRT_STEAL_SPREAD ? 1u + 2u * ((blockIdx.x / MRT_NPART) & 3u) : 1u;
     bool in_tail = false;                    // the partition's last paths: small claims
     uint64_t pool_next = 0, pool_end = 0;    // wave-uniform: the wave's claimed, not yet taken paths
     if (P.static_first) {
@@ -336,13 +349,22 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     // touched once per 64 path starts -- so it holds no registers across the path loop (held in
     // registers it cost VGPR spills to scratch: 1.2 GB/launch of extra HBM writes on C2).
     uint32_t* const Lc = reinterpret_cast<uint32_t*>(Lq + 12u * 64u);
+    // (Cornell walk, eight waves per SIMD: 80 scalar registers.  "lane == 0" is made where it is used --
+    // as a mask held across the path loop it was two of them -- and the steal step lives in the row)
+    auto first_lane = [&]() -> bool {
+        uint32_t l = lane;
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (kBox6Walk<F>) asm volatile("" : "+v"(l));
+#endif
+        return l == 0;
+    };
     auto cold_store = [&]() {
-        if (lane == 0) {
+        if (first_lane()) {
             Lc[0] = (uint32_t)pool_next;
             Lc[1] = (uint32_t)(pool_next >> 32);
             Lc[2] = (uint32_t)pool_end;
             Lc[3] = (uint32_t)(pool_end >> 32);
-            Lc[4] = part | (part_tries << 8) | ((uint32_t)in_tail << 16);
+            Lc[4] = part | (part_tries << 8) | ((uint32_t)in_tail << 16) | (kBox6Walk<F> ? steal_step << 24 : 0u);
         }
     };
     auto cold_load = [&]() {
@@ -353,6 +375,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
         part = w & 0xFFu;
         part_tries = (w >> 8) & 0xFFu;
         in_tail = ((w >> 16) & 1u) != 0;
+        if constexpr (kBox6Walk<F>) steal_step = w >> 24;
     };
     if constexpr (PathQ<F>::on) cold_store();
     uint32_t done_rays = 0;
@@ -381,7 +404,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                 uint64_t wt_a = 0;
                 WT_MARK(wt_a);
 #endif
-                if (lane == 0) {
+                if (first_lane()) {
                     nb = p0 + atomicAdd(Q.counter + part * MRT_COUNTER_STRIDE, (unsigned long long)batch);
                     // every 32nd claim: a system-scope store to host memory, read by mrt_progress
                     // without any GPU queue (a device-to-host copy could wait behind this launch)
@@ -501,6 +524,11 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
         // registers, which stalled the wave for the store's whole round trip every iteration
         // (measured: SQ_WAIT_ANY 23 -> 36 quad-cycles per ray once the path loop had fewer
         // instructions); beside the material load the two round trips overlap.
+        // The Cornell walk (kBox6Walk) reads its material from the wave's LDS hit table: the common
+        // path of its iteration has no vector-memory load for a store to share vmcnt with, so it stores
+        // where the path ends (kHeldStore off) and the four held registers and the lane mask are gone
+        // from its loop: 64 VGPRs, eight waves per SIMD.
+        constexpr bool kHeldStore = !kBox6Walk<F>;
         f3 st_v{0.0f, 0.0f, 0.0f};
         uint32_t st_off = 0;  // byte offset of the path's radiance (a launch chunk is < 4 GiB)
         bool st_pend = false;
@@ -539,25 +567,47 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             // the next ray's arguments: written and read within one iteration (declared here, a
             // field a branch leaves unset is dead, not carried round the loop in copied registers)
             PendRay pr;
+            // Cornell walk: the next ray's origin and inside count start as the lane's own and are
+            // assigned back below for EVERY lane, not under want_ray (a lane without a next ray holds
+            // no path: its ray is never read again).  Assigned under the mask, the old values had to
+            // survive in the lanes outside it, so the new ones were made elsewhere and copied in:
+            // four register copies per iteration and four VGPRs (64 -> 60).
+            if constexpr (kBox6Walk<F>) { pr.o = ps.r.o; pr.inside = ps.r.inside; }
             if (active) {
                 f3 L{0.0f, 0.0f, 0.0f};  // (left undefined, it was carried round the loop in copied registers)
                 // (the held store is issued inside, after the hit, beside the material load)
                 uint32_t max_bounces = P.max_bounces;
                 if constexpr (kBox6Walk<F>) max_bounces = cw.max_bounces;
                 const bool ended = trace_split<F, LK>(S, ps, max_bounces, lev, Ls, &L, &pr, ph, [&]() {
-                    if (st_pend) {
-                        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off);
-                        dst[0] = st_v.x;
-                        dst[1] = st_v.y;
-                        dst[2] = st_v.z;
+                    if constexpr (kHeldStore) {
+                        if (st_pend) {
+                            float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off);
+                            dst[0] = st_v.x;
+                            dst[1] = st_v.y;
+                            dst[2] = st_v.z;
+                        }
+                        st_pend = false;
                     }
-                    st_pend = false;
                 }, CritSink{idx, kCritOff<F>}, sph_inv_rad, cornell_ptr(cw));
                 PH_MARK(ph, 2);
                 if (ended) {
-                    st_v = end_path(ps, lev, L);
-                    st_off = idx * 12u;
-                    st_pend = true;
+                    if constexpr (kHeldStore) {
+                        st_v = end_path(ps, lev, L);
+                        st_off = idx * 12u;
+                        st_pend = true;
+                    } else {
+                        // the same three words at the same address, idx * 12 as two shift-adds (no
+                        // quarter-rate 32-bit multiply per finished path)
+                        const f3 R = end_path(ps, lev, L);
+                        uint32_t i4 = idx << 2;
+#if defined(__HIP_DEVICE_COMPILE__)
+                        asm volatile("" : "+v"(i4));  // (kept apart from the sum: rejoined, it is the multiply again)
+#endif
+                        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + ((i4 << 1) + i4));
+                        dst[0] = R.x;
+                        dst[1] = R.y;
+                        dst[2] = R.z;
+                    }
                     if constexpr (kBox6Walk<F>) {
                         if (cornell_flag(&cw, kCwPathRays)) kernarg_params().path_rays[idx] = ps.rays();
                     } else if (P.path_rays) P.path_rays[idx] = ps.rays();
@@ -573,11 +623,14 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                 // starts are made at once, one per lane at full width (path key, PCG seeding, the
                 // camera's disk-rejection and time draws), instead of by the ~1/3 of lanes whose
                 // path just ended: the same paths with the same streams, in the same order
+                // (the time word: only kernels with moving spheres read a ray's time; the others neither
+                // compute nor store it, the refill steps their streams over its draw)
+                constexpr bool kTimeWord = (F & FT_MOVING) != 0;
                 auto pop = [&](uint32_t e) {
                     const float* q = Lq + e;
                     pr.o = f3{q[0], q[64], q[128]};
                     pr.dir = f3{q[192], q[256], q[320]};
-                    pr.time = q[384];
+                    pr.time = kTimeWord ? q[384] : 0.0f;
                     ps.rng.state = (uint64_t)__float_as_uint(q[448]) | ((uint64_t)__float_as_uint(q[512]) << 32);
                     ps.rng.inc = (uint64_t)__float_as_uint(q[576]) | ((uint64_t)__float_as_uint(q[640]) << 32);
                     idx = __float_as_uint(q[704]);
@@ -611,17 +664,23 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                                 Pcg rng;
                                 float u, v, time;
                                 f3 o, dir;
-                                path_key_of(Q, (uint32_t)i, rng, &u, &v);
-                                camera_ray_args(Q.sc, rng, u, v, &o, &dir, &time);
+                                // the index as the 32-bit value it is (i < n_paths is known here, and
+                                // path_coords' conversion to double was made from all 64 bits)
+                                uint32_t i32 = (uint32_t)i;
+#if defined(__HIP_DEVICE_COMPILE__)
+                                asm volatile("" : "+v"(i32));
+#endif
+                                path_key_of(Q, i32, rng, &u, &v);
+                                camera_ray_args<kTimeWord>(Q.sc, rng, u, v, &o, &dir, &time);
                                 float* q = Lq + lane;
                                 q[0] = o.x; q[64] = o.y; q[128] = o.z;
                                 q[192] = dir.x; q[256] = dir.y; q[320] = dir.z;
-                                q[384] = time;
+                                if constexpr (kTimeWord) q[384] = time;
                                 q[448] = __uint_as_float((uint32_t)rng.state);
                                 q[512] = __uint_as_float((uint32_t)(rng.state >> 32));
                                 q[576] = __uint_as_float((uint32_t)rng.inc);
                                 q[640] = __uint_as_float((uint32_t)(rng.inc >> 32));
-                                q[704] = __uint_as_float((uint32_t)i);
+                                q[704] = __uint_as_float(i32);
                             }
                             q_n = (uint32_t)__popcll(__ballot(valid));  // a prefix of the lanes
                             const uint32_t r2 = rank - avail;
@@ -640,19 +699,22 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                 });
             }
             if (!__any(active)) {  // the last store
-                if (st_pend) {
-                    float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off);
-                    dst[0] = st_v.x;
-                    dst[1] = st_v.y;
-                    dst[2] = st_v.z;
+                if constexpr (kHeldStore) {
+                    if (st_pend) {
+                        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off);
+                        dst[0] = st_v.x;
+                        dst[1] = st_v.y;
+                        dst[2] = st_v.z;
+                    }
                 }
                 break;
             }
             PH_MARK(ph, 0);
             BSTATC(15, active);
+            if constexpr (kBox6Walk<F>) { ps.r.o = pr.o; ps.r.inside = pr.inside; }
             if (want_ray) {
                 BSTATC(12, pr.kind != 0);
-                ps.r = make_ray(pr.o, pr.dir, pr.time, pr.inside);
+                ps.r = make_ray(kBox6Walk<F> ? ps.r.o : pr.o, pr.dir, pr.time, kBox6Walk<F> ? ps.r.inside : pr.inside);
                 // the Cornell fast walk's light test, once per ray: the scatter's light pdf below and
                 // the next iteration's walk both read it (one VGPR across the back edge)
                 if constexpr (kBox6Walk<F>) ps.lt = cornell_light_t<F>(cw.light, ps.r);

@@ -1394,7 +1394,7 @@ extern "C" mrt_status mrt_scene_kernel_info(const mrt_scene* s, mrt_kernel_info*
                : L.fn == kernel_table_fast_pex().kernel[s->variant] ? MRT_BUILD_PATH_EXACT
                : L.fn == kernel_table_fast_ftz().kernel[s->variant] ? MRT_BUILD_FAST_FTZ
                                                                      : MRT_BUILD_FAST;
-    out->pad = 0;
+    out->n_cu = s->n_cu;
     out->handed_over = 0;
     out->handover_lost = 0;
     if (s->d_counter) {

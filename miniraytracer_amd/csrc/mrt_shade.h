@@ -430,6 +430,9 @@ MRT_DFN Ray camera_ray(const DScene& S, Pcg& rng, float s, float t) {
 // camera::get_ray without the ray constructor: origin, direction argument and time of the ray
 // (the constructor -- normalize, 1/dir, dirMask -- runs once per iteration for every lane that
 // has a new ray, see PendRay)
+// kTime false (a caller whose kernel never reads a ray's time): the stream steps over the time draw,
+// its value is not made (*time = 0)
+template <bool kTime = true>
 MRT_DFN void camera_ray_args(const DScene& S, Pcg& rng, float s, float t, f3* o, f3* dir, float* time) {
     const MRT_CONST_AS mrt_camera* cp = const_ptr(S.camp);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -438,7 +441,12 @@ MRT_DFN void camera_ray_args(const DScene& S, Pcg& rng, float s, float t, f3* o,
     const MRT_CONST_AS mrt_camera& C = *cp;
     f3 rd = fmul(C.lens_radius, random_in_disk(rng));
     f3 offset = add(mulf(ld3(C.u), rd.x), mulf(ld3(C.v), rd.y));
-    *time = ref_fma(C.time1 - C.time0, randf(rng), C.time0);  // camera.h:41
+    if constexpr (kTime) {
+        *time = ref_fma(C.time1 - C.time0, randf(rng), C.time0);  // camera.h:41
+    } else {
+        pcg_next(rng);
+        *time = 0.0f;
+    }
     f3 origin = ld3(C.origin);
     *dir = sub(sub(add(add(ld3(C.llcorner), fmul(s, ld3(C.horz))), fmul(t, ld3(C.vert))), origin), offset);
     *o = add(origin, offset);
