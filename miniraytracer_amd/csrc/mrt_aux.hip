@@ -18,9 +18,7 @@ template <uint32_t F>
 __global__ void __launch_bounds__(64) mrt_aux_kernel(PathParams P, float4* __restrict__ normal, float4* __restrict__ albedo) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t* const wb = lds;
-    uint32_t* const wmesh = wb + P.lds_frames * 128 + P.lds_rays * 704;
-    const LStack Ls{wb, (float*)(wb + P.lds_frames * 128), wmesh, (float*)(wmesh + P.lds_mesh * 64), lane, nullptr, 0u};
+    const LStack Ls = lds_stacks(WaveLds{P.lds_frames, P.lds_rays, P.lds_mesh, P.lds_save}, lds, lane);
     const DScene& S = P.sc;
     const uint32_t lp = blockIdx.x * 64u + lane;
     if (lp >= P.npix) return;

@@ -253,56 +253,62 @@ template <uint32_t F> struct PathQ {
     // LDS words per lane slot: o, dir, time, PCG state + inc, index (12); + the wave's claim state
     static constexpr uint32_t words = on ? 13u : 0u;
 };
+// set bits of a wave mask below this lane (v_mbcnt: no per-lane 64-bit mask kept live)
+MRT_DFN uint32_t rank_below(uint64_t m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+MRT_DFN uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+// wave-uniform values kept in SGPRs (the compiler otherwise held the pool bounds in VGPRs and
+// spilled them to scratch, reloaded every claim)
+MRT_DFN uint64_t uni64(uint64_t x) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+}
+// a path's radiance: three words (sample-major, coalesced)
+MRT_DFN void store_radiance(float* dst, f3 L) {
+    dst[0] = L.x;
+    dst[1] = L.y;
+    dst[2] = L.z;
+}
 template <uint32_t F>
 __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per_eu(MRT_OCC(F)))) MRT_PATH_KERNEL(PathParams P) {
     constexpr uint32_t LK = PathLevLds<F>::K;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
-    // per wave: its stacks and queues ([slot][word][lane])
-    // (a kBox6Walk kernel's slice starts with the wave's copy of the Cornell hit table, mrt_sig.h: in a
-    // one-wave group at LDS address 0, a constant)
-    constexpr uint32_t hit_words = kBox6Walk<F> ? kHitLdsBytes / 4u : 0u;
-    const uint32_t words = (P.lds_frames * 2 + P.lds_rays * 11 + P.lds_mesh + P.lds_save + LK * 4 + PathQ<F>::words) * 64 + hit_words;
-    // A Cornell walk kernel's queue of path starts (with the claim state and the basis axes in its last
-    // row) comes straight behind the hit table, in front of the stacks and fold levels, whose sizes are
-    // launch parameters: in a one-wave group every queue address is then a constant of the kernel, not
-    // a scalar register held across the path loop (two of the 80 that eight waves per SIMD leave).
-    constexpr uint32_t q_front = kBox6Walk<F> ? PathQ<F>::words * 64u : 0u;
-    uint32_t* wb = lds + wave * words + hit_words + q_front;
-    uint32_t* const wmesh = wb + P.lds_frames * 128 + P.lds_rays * 704;
-    float4* tree = nullptr;
+    // the group's LDS (mrt_launch.h WaveLds): this wave's slice, the group's treelet behind the slices
+    const WaveLds L{P.lds_frames, P.lds_rays, P.lds_mesh, P.lds_save, LK, PathQ<F>::words, kBox6Walk<F> != 0u, TreeOf<F>::wg / 64u};
+    uint32_t* const slice = lds + wave * L.stride();
+    LStack Lw = lds_stacks(L, slice, lane);
     if constexpr (TreeOf<F>::on) {
-        // the workgroup's copy of the top wide nodes (after every wave's own region), filled once
-        // before any wave starts a path; no other barrier follows in this persistent kernel
-        tree = reinterpret_cast<float4*>(lds + (TreeOf<F>::wg / 64u) * words);
+        // the workgroup's copy of the top wide nodes, filled once before any wave starts a path; no
+        // other barrier follows in this persistent kernel
+        float4* const tree = reinterpret_cast<float4*>(lds + L.tree_at());
         for (uint32_t i = threadIdx.x; i < P.tree_n * 4u; i += blockDim.x) tree[i] = P.tree_src[i];
         __syncthreads();
+        Lw.tree = tree;
+        Lw.tree_b = P.tree_n;
     }
-    const LStack Ls{wb, (float*)(wb + P.lds_frames * 128), wmesh, (float*)(wmesh + P.lds_mesh * 64), lane, tree,
-                    TreeOf<F>::on ? P.tree_n : 0u,
-                    !kBox6Walk<F> ? 0u
-                    : TreeOf<F>::wg == 64u ? (uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)lds  // (one wave: its slice is the group's)
-                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(wb - q_front - hit_words)),
-                    // (the basis axes of the table's normals: in the claim row of the queue below, mrt_sig.h kHitAxisWord0)
-                    !kBox6Walk<F> ? 0u
-                    : TreeOf<F>::wg == 64u ? (uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(lds + hit_words + 12u * 64u + kHitAxisWord0)
-                    : (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(
-                          wb - q_front + 12u * 64u + kHitAxisWord0))};
+    // A Cornell walk kernel's hit table, queue of path starts and basis axes: in a one-wave group the
+    // wave's slice is the group's, so each address is a constant of the kernel, not a scalar register
+    // held across the path loop (two of the 80 that eight waves per SIMD leave)
     static_assert(!kBox6Walk<F> || PathQ<F>::on, "the Cornell walk's basis axes live in the queue's claim row");
-    // the wave's queue of path starts ([word][entry], PathQ): after the fold levels
-    // (Cornell walk: in front of the stacks, see q_front)
-    float* const Lq = !kBox6Walk<F>          ? (float*)(wmesh + (P.lds_mesh + P.lds_save + LK * 4) * 64)
-                      : TreeOf<F>::wg == 64u ? (float*)(lds + hit_words)
-                                             : (float*)(wb - q_front);
+    uint32_t* const front = kBox6Walk<F> && TreeOf<F>::wg == 64u ? lds : slice;
+    if constexpr (kBox6Walk<F>) {
+        auto addr = [](uint32_t* p) -> uint32_t {
+            const uint32_t a = (uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)p;
+            return TreeOf<F>::wg == 64u ? a : (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
+        };
+        Lw.hits = addr(front + L.hit_table());
+        Lw.axes = addr(front + L.axes_at());
+    }
+    const LStack Ls = Lw;
+    // the wave's queue of path starts ([word][entry], PathQ)
+    float* const Lq = kBox6Walk<F> ? (float*)(front + L.queue_at()) : (float*)(Ls.mesh + L.queue_past_mesh());
     const DScene& S = P.sc;
     const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const LevStore<LK> lev{(MRT_GLOBAL_AS v4f*)P.lev, P.lev_rows, (uint32_t)slot,
-                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(wmesh + (P.lds_mesh + P.lds_save) * 64))};
-    // set bits of a wave mask below this lane (v_mbcnt: no per-lane 64-bit mask kept live)
-    auto rank_below = [](uint64_t m) -> uint32_t {
-        return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    };
+                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(MRT_LDS_AS uint32_t*)(Ls.mesh + L.levels_past_mesh()))};
 
     // main.cpp:180/235 stop on !G_isRunning: a launch of a cancelled render does no work (mrt_render
     // splits a cancellable render into several launches)
@@ -324,13 +330,6 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     // launches only -- P.static_first, set by the host when a wave gets fewer than 64 claims: there
     // the opening atomics are a visible share; in long launches the static batch of a wave that
     // starts late in a pipelined step delays that launch's end).
-    auto umin64 = [](uint64_t a, uint64_t b) -> uint64_t { return a < b ? a : b; };
-    // wave-uniform values kept in SGPRs (the compiler otherwise held the pool bounds in VGPRs and
-    // spilled them to scratch, reloaded every claim)
-    auto uni64 = [](uint64_t x) -> uint64_t {
-        return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(x >> 32)) << 32) |
-               (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
-    };
     const uint32_t wpb = blockDim.x >> 6;  // waves per workgroup
     uint32_t part = blockIdx.x % MRT_NPART;  // wave-uniform: the partition claims come from
     uint32_t part_tries = 0;                 // partitions found handed out
@@ -348,7 +347,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     // Queue kernels keep the claim state (pool bounds, partition) in LDS between claims -- it is
     // touched once per 64 path starts -- so it holds no registers across the path loop (held in
     // registers it cost VGPR spills to scratch: 1.2 GB/launch of extra HBM writes on C2).
-    uint32_t* const Lc = reinterpret_cast<uint32_t*>(Lq + 12u * 64u);
+    uint32_t* const Lc = reinterpret_cast<uint32_t*>(Lq) + WaveLds::kQueueRows * WaveLds::kLanes;
     // (Cornell walk, eight waves per SIMD: 80 scalar registers.  "lane == 0" is made where it is used --
     // as a mask held across the path loop it was two of them -- and the steal step lives in the row)
     auto first_lane = [&]() -> bool {
@@ -383,12 +382,6 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
 #ifdef MRT_PHASES
     ph.t = __builtin_amdgcn_s_memtime();
 #endif
-    // Lanes without a path take the next path indices from the wave's pool (ballot + mbcnt
-    // compaction), the pool refilled by one atomic per claim (work_queue::getWork,
-    // work_queue.cpp:158-166).  start(u, v) begins a lane's path at camera coordinates (u, v) with
-    // its PCG stream seeded from the path key.
-    // path index -> its camera coordinates (u, v) and its PCG stream seeded from the path key
-    auto path_key = [&](uint32_t i, Pcg& rng, float* uo, float* vo) { path_key_of(P, i, rng, uo, vo); };
     // the next c path indices of the wave's pool, the lane of rank r taking index *i (>= n_paths:
     // none); the pool refilled by one atomic per claim (work_queue::getWork, work_queue.cpp:158-166)
     // (q: where a refill of a Cornell walk kernel reads the kernel's arguments, kernarg_params(); else P)
@@ -466,7 +459,8 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
         active = true;
     };
     // Lanes without a path take the next path indices from the wave's pool (ballot + mbcnt
-    // compaction).  start(u, v) begins a lane's path at camera coordinates (u, v).
+    // compaction).  start(u, v) begins a lane's path at camera coordinates (u, v) with its PCG stream
+    // seeded from the path key (path_key_of).
     auto take_paths = [&](auto&& start) {
         const uint64_t need = __ballot(!active);
         if (!need || exhausted) return;
@@ -478,7 +472,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             idx = (uint32_t)i;
             BSTAT(10);
             float u, v;
-            path_key(idx, ps.rng, &u, &v);
+            path_key_of(P, idx, ps.rng, &u, &v);
             start(u, v);
             begin_path();
         }
@@ -488,16 +482,10 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     auto finish_path = [&](f3 L) {
         L = end_path(ps, lev, L);
         PH_MARK(ph, 5);
-        float* dst = P.rad + (size_t)idx * 3;
 #if defined(MRT_EXPERIMENTS) && defined(MRT_EXP_NOSTORE)  // experiment: what the radiance store costs
-        if (__float_as_uint(L.x) == 0x7fc00123u) {
+        if (__float_as_uint(L.x) == 0x7fc00123u)
 #endif
-        dst[0] = L.x;
-        dst[1] = L.y;
-        dst[2] = L.z;
-#if defined(MRT_EXPERIMENTS) && defined(MRT_EXP_NOSTORE)
-        }
-#endif
+        store_radiance(P.rad + (size_t)idx * 3, L);
         if (P.path_rays) P.path_rays[idx] = ps.rays();
         done_rays += ps.rays();
         active = false;
@@ -580,12 +568,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                 if constexpr (kBox6Walk<F>) max_bounces = cw.max_bounces;
                 const bool ended = trace_split<F, LK>(S, ps, max_bounces, lev, Ls, &L, &pr, ph, [&]() {
                     if constexpr (kHeldStore) {
-                        if (st_pend) {
-                            float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off);
-                            dst[0] = st_v.x;
-                            dst[1] = st_v.y;
-                            dst[2] = st_v.z;
-                        }
+                        if (st_pend) store_radiance(reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off), st_v);
                         st_pend = false;
                     }
                 }, CritSink{idx, kCritOff<F>}, sph_inv_rad, cornell_ptr(cw));
@@ -603,10 +586,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
 #if defined(__HIP_DEVICE_COMPILE__)
                         asm volatile("" : "+v"(i4));  // (kept apart from the sum: rejoined, it is the multiply again)
 #endif
-                        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + ((i4 << 1) + i4));
-                        dst[0] = R.x;
-                        dst[1] = R.y;
-                        dst[2] = R.z;
+                        store_radiance(reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + ((i4 << 1) + i4)), R);
                     }
                     if constexpr (kBox6Walk<F>) {
                         if (cornell_flag(&cw, kCwPathRays)) kernarg_params().path_rays[idx] = ps.rays();
@@ -700,12 +680,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             }
             if (!__any(active)) {  // the last store
                 if constexpr (kHeldStore) {
-                    if (st_pend) {
-                        float* dst = reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off);
-                        dst[0] = st_v.x;
-                        dst[1] = st_v.y;
-                        dst[2] = st_v.z;
-                    }
+                    if (st_pend) store_radiance(reinterpret_cast<float*>(reinterpret_cast<char*>(P.rad) + st_off), st_v);
                 }
                 break;
             }
@@ -907,9 +882,7 @@ template <uint32_t F>
 __global__ void __launch_bounds__(64) mrt_retrace_kernel(PathParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t* const wb = lds;
-    uint32_t* const wmesh = wb + P.lds_frames * 128 + P.lds_rays * 704;
-    const LStack Ls{wb, (float*)(wb + P.lds_frames * 128), wmesh, (float*)(wmesh + P.lds_mesh * 64), lane, nullptr, 0u};
+    const LStack Ls = lds_stacks(WaveLds{P.lds_frames, P.lds_rays, P.lds_mesh, P.lds_save}, lds, lane);
     const LevStore<0> lev{nullptr, 0u, 0u, 0u};
     const DScene& S = P.sc;
     PhaseClock ph{};
@@ -932,10 +905,7 @@ __global__ void __launch_bounds__(64) mrt_retrace_kernel(PathParams P) {
         while (!trace_segment<F, 0>(S, ps, P.max_bounces, lev, Ls, &L, ph)) {
         }
         L = end_path(ps, lev, L);
-        float* dst = P.rad + (size_t)idx * 3u;
-        dst[0] = L.x;
-        dst[1] = L.y;
-        dst[2] = L.z;
+        store_radiance(P.rad + (size_t)idx * 3u, L);
     }
     if (lane == 0 && atomicAdd(P.rt.done, 1u) == gridDim.x - 1u) {
         atomicExch(P.rt.n, 0u);  // every group has read the count: the list is empty for the next launch

@@ -434,11 +434,11 @@ struct mrt_scene {
     bool trust_pixels = false;
 };
 
-// LDS words per lane of a launch's walk stacks: the generic machine's frames (two words each) and
-// transformed rays (eleven each), the mesh / bvh_node walk's stack, `lds_save` words for the query ray
-// parked during instances.  The path, retrace and aux launches all size their LDS from it.
-static uint32_t lds_stack_words(const mrt_scene* s, uint32_t lds_save) {
-    return s->lds_frames * 2 + s->lds_rays * 11 + s->lds_mesh + lds_save;
+// The LDS of a one-wave launch that only walks (the retrace and aux kernels): the generic machine's
+// frames and transformed rays, the mesh / bvh_node walk's stack, `lds_save` words for the query ray
+// parked during instances (mrt_launch.h WaveLds, which the kernels index it by).
+static WaveLds walk_lds(const mrt_scene* s, uint32_t lds_save) {
+    return WaveLds{s->lds_frames, s->lds_rays, s->lds_mesh, lds_save};
 }
 
 static mrt_status dev_alloc(mrt_scene* s, void** p, size_t bytes) {
@@ -596,27 +596,30 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
         const int vg = std::max(8, (fa.numRegs + 7) & ~7);
         const int nb_vgpr = std::max(1, std::min(8, 512 / vg) * 4 / (int)waves_per_wg);  // waves per CU / waves per group
         auto groups = [&](size_t lds) { return std::max(1, lds ? std::min<int>(nb_vgpr, (int)((160u * 1024u) / lds)) : nb_vgpr); };
-        L.lds_bytes = (size_t)waves_per_wg * 64 * 4 * (lds_stack_words(s, L.lds_save) + tabs[k]->lev_k[s->variant] * 4 + tabs[k]->pq[s->variant]);
-        // + each wave's copy of the Cornell hit table (mrt_sig.h; T.cornell_hits, uploaded behind the program)
-        if (tabs[k]->box6_walk[s->variant]) {
-            if (T.cornell_hits.empty()) return mrt_internal_fail(MRT_ERR_INVALID, "Cornell walk without a hit table");
-            L.lds_bytes += (size_t)waves_per_wg * kHitLdsBytes;
-        }
-        if (L.lds_bytes > (size_t)prop.sharedMemPerBlock) return mrt_internal_fail(MRT_ERR_INVALID, "scene graph too deep for the LDS stacks");
-        int nb = groups(L.lds_bytes);
+        // the group's LDS as the kernel indexes it (mrt_launch.h WaveLds): the stacks, the variant's fold
+        // levels and queue of path starts, each wave's copy of the Cornell hit table (mrt_sig.h;
+        // T.cornell_hits, uploaded behind the program)
+        WaveLds lds = walk_lds(s, L.lds_save);
+        lds.lev_k = tabs[k]->lev_k[s->variant];
+        lds.pq = tabs[k]->pq[s->variant];
+        lds.box6 = tabs[k]->box6_walk[s->variant] != 0;
+        lds.waves = waves_per_wg;
+        if (lds.box6 && T.cornell_hits.empty()) return mrt_internal_fail(MRT_ERR_INVALID, "Cornell walk without a hit table");
+        if (lds.bytes() > (size_t)prop.sharedMemPerBlock) return mrt_internal_fail(MRT_ERR_INVALID, "scene graph too deep for the LDS stacks");
+        int nb = groups(lds.bytes());
         if (tabs[k]->tree[s->variant]) {
             // the LDS the resident groups leave free, split among them: the treelet of each group
             const size_t per = std::min<size_t>((160u * 1024u) / nb, (size_t)prop.sharedMemPerBlock);
-            const uint32_t node_bytes = 64u;  // BvhWide
+            const uint32_t node_bytes = WaveLds::kNodeWords * 4u;  // BvhWide
             const uint32_t n_nodes = (uint32_t)T.bwide.size();
-            uint32_t cap = per > L.lds_bytes ? (uint32_t)((per - L.lds_bytes) / node_bytes) : 0u;
+            uint32_t cap = per > lds.bytes() ? (uint32_t)((per - lds.bytes()) / node_bytes) : 0u;
 #ifdef MRT_EXPERIMENTS
             if (const char* e = getenv("MRT_TREELET_NODES"))  // sweep hook
                 if (*e) cap = std::min<uint32_t>(cap, (uint32_t)atoi(e));
 #endif
-            L.tree_n = std::min(cap, n_nodes);
-            L.lds_bytes += (size_t)L.tree_n * node_bytes;
+            lds.tree_n = L.tree_n = std::min(cap, n_nodes);
         }
+        L.lds_bytes = lds.bytes();
         L.vgprs = (uint32_t)fa.numRegs;
 #ifdef MRT_EXPERIMENTS
         if (const char* e = getenv("MRT_BLOCKS_PER_CU"))  // experiment hook
@@ -978,7 +981,8 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
         if (handover) {
             PathParams PR = P;
             PR.sc.prog = s->S.prog;
-            hipLaunchKernelGGL(PL.retrace, dim3(kRetraceGroups), dim3(64), (size_t)64 * 4 * lds_stack_words(s, s->lds_save), q, PR);
+            PR.lds_save = s->lds_save;  // (the exact arithmetic parks a ray where the Cornell walk does not)
+            hipLaunchKernelGGL(PL.retrace, dim3(kRetraceGroups), dim3(64), walk_lds(s, PR.lds_save).bytes(), q, PR);
             HIPCHK(hipGetLastError());
         }
         // the last chunk's full fold finishes the render (no preview: no snapshot of acc needed;
@@ -1201,7 +1205,7 @@ extern "C" mrt_status mrt_render_aux_device(mrt_scene* s, const mrt_render_desc*
     const aux_kernel_t fn = aux_kernel_table().kernel[s->variant];
     const PathLaunch& PL = s->pl[0];  // the exact build's stack sizes
     const PathParams P = launch_params(s, PL, d);
-    const size_t lds_bytes = (size_t)64 * 4 * lds_stack_words(s, PL.lds_save);
+    const size_t lds_bytes = walk_lds(s, P.lds_save).bytes();
     hipStream_t q = (hipStream_t)stream;
     hipLaunchKernelGGL(fn, dim3((s->npix + 63u) / 64u), dim3(64), lds_bytes, q, P, (float4*)d_normal, (float4*)d_albedo);
     HIPCHK(hipGetLastError());
