@@ -132,7 +132,17 @@ build/temporal_check: $(TEMPORAL_CHECK_SRC) include/mrt_temporal.h include/mrt_d
 temporal-check: build/temporal_check
 	build/temporal_check
 
+# The Cornell walk kernels' 32-bit pool arithmetic (mrt_launch.h pool_claim32 ...) against the 64-bit
+# expressions it replaces, stand-alone under the same sanitizers (host code only, nothing preloaded;
+# not part of `all`): tools/claim_check.cpp
+build/claim_check: tools/claim_check.cpp $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) --offload-host-only -x hip $(SANFLAGS) tools/claim_check.cpp -o $@
+
+claim-check: build/claim_check
+	build/claim_check
+
 clean:
 	rm -rf build miniraytracer_amd/libmrt.so bin oracle/liboracle.so
 
-.PHONY: all clean tables-check temporal-check
+.PHONY: all clean tables-check temporal-check claim-check

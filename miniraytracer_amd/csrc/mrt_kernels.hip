@@ -241,10 +241,6 @@ MRT_DFN const PathParams& kernarg_params() {
     asm volatile("" : "+s"(pp));
     return *(const PathParams*)pp;
 }
-// claim()'s arguments: P, or the pointer a refill hands it (an optional trailing argument: as a plain
-// reference parameter it reordered two register copies in the exact build's kernels)
-MRT_DFN const PathParams& claim_params(const PathParams& P) { return P; }
-MRT_DFN const PathParams& claim_params(const PathParams&, const PathParams* q) { return *q; }
 #ifndef MRT_OPAQUE_RESUME
 #define MRT_OPAQUE_RESUME 0  // the same in the room + mesh kernels' resumable loop: measured C3 -0.6%, C4 0 (A/B hook)
 #endif
@@ -317,7 +313,10 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
     uint64_t wt0 = 0, wt_ex = 0, wt1 = 0, wt_f = 0, wt_aok = 0, wt_afail = 0, wt_n = 0;
     WT_MARK(wt0);
 #endif
-    bool active = false;
+    // whether the lane holds a path.  Cornell walk: a 0 / 1 word, not a bool -- the flag crosses the
+    // loop's blocks in a vector register either way, and a lane mask made from a word is one compare
+    // where one made from a bool in a register was v_and + v_cmp
+    std::conditional_t<kBox6Walk<F> != 0u, uint32_t, bool> active = false;
     uint32_t idx = 0;
     PathState ps;
     // The launch's paths are split into MRT_NPART equal contiguous partitions, one work counter
@@ -384,9 +383,8 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
 #endif
     // the next c path indices of the wave's pool, the lane of rank r taking index *i (>= n_paths:
     // none); the pool refilled by one atomic per claim (work_queue::getWork, work_queue.cpp:158-166)
-    // (q: where a refill of a Cornell walk kernel reads the kernel's arguments, kernarg_params(); else P)
-    auto claim = [&](uint32_t c, uint32_t r, bool want, uint64_t* i, auto... q) {
-        const PathParams& Q = claim_params(P, q...);
+    auto claim = [&](uint32_t c, uint32_t r, bool want, uint64_t* i) {
+        const PathParams& Q = P;
         const uint32_t have = (uint32_t)(pool_end - pool_next);
         uint64_t nb = 0, ne = 0;
         if (have < c) {
@@ -446,6 +444,82 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             pool_next += c;
         }
         exhausted = part_tries >= MRT_STEAL_TRIES && pool_next >= pool_end;
+#if defined(MRT_EXPERIMENTS) && defined(MRT_WTIMES)
+        if (exhausted && wt_ex == 0) WT_MARK(wt_ex);
+#endif
+    };
+    // The same for a Cornell walk kernel's refill, the pool in 32 bits (mrt_launch.h pool_claim32: a
+    // launch's path indices are below 2^32): the pool bounds, the partition's end and the tail-zone test
+    // are scalar compares and selects instead of 64-bit vector ones on broadcast values, a lane's index
+    // one 32-bit add.  The counters, the progress word and the claim row's words are what claim() makes;
+    // the row's words 1 and 3 (the bounds' high halves) stay the zeros the kernel's first store wrote.
+    uint32_t pool32_next = 0, pool32_end = 0;
+    auto cold_store32 = [&]() {
+        if (first_lane()) {
+            Lc[0] = pool32_next;
+            Lc[2] = pool32_end;
+            Lc[4] = part | (part_tries << 8) | ((uint32_t)in_tail << 16) | (steal_step << 24);
+        }
+    };
+    auto cold_load32 = [&]() {
+        auto rd = [&](uint32_t k) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)Lc[k]); };
+        pool32_next = rd(0);
+        pool32_end = rd(2);
+        const uint32_t w = rd(4);
+        part = w & 0xFFu;
+        part_tries = (w >> 8) & 0xFFu;
+        in_tail = ((w >> 16) & 1u) != 0;
+        steal_step = w >> 24;
+    };
+    auto claim32 = [&](uint32_t c, uint32_t r, uint32_t* i, const PathParams& Q) {
+        const uint32_t have = pool32_end - pool32_next;
+        uint32_t nb = 0, ne = 0;
+        if (have < c) {
+            while (part_tries < MRT_STEAL_TRIES) {  // wave-uniform
+                const uint32_t pe = (uint32_t)Q.part_base[part + 1];
+                const uint64_t p0 = Q.part_dyn[part];
+                const uint32_t batch = in_tail ? MRT_TAIL_BATCH : MRT_BATCH;
+#if defined(MRT_EXPERIMENTS) && defined(MRT_WTIMES)
+                uint64_t wt_a = 0;
+                WT_MARK(wt_a);
+#endif
+                uint64_t got = 0;
+                if (first_lane()) {
+                    got = p0 + atomicAdd(Q.counter + part * MRT_COUNTER_STRIDE, (unsigned long long)batch);
+                    if (Q.hprog && (((got - p0) / batch) & 31u) == 0)
+                        __hip_atomic_store(Q.hprog + part, got + batch - Q.part_base[part], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+                got = uni64(got);  // lane 0's claim to every lane, as a scalar
+                const bool ok = pool_claim32(got, batch, pe, &nb, &ne);
+#if defined(MRT_EXPERIMENTS) && defined(MRT_WTIMES)
+                {
+                    uint64_t wt_b = 0;
+                    WT_MARK(wt_b);
+                    if (ok) { wt_aok += wt_b - wt_a; wt_n += 1; }
+                    else { wt_afail += wt_b - wt_a; wt_n += 1ull << 32; }
+                }
+#endif
+                if (ok) {
+#if MRT_STEAL_SMALL
+                    in_tail = pool_tail32(pe, ne, Q.tail_zone);
+#else
+                    in_tail = in_tail || pool_tail32(pe, ne, Q.tail_zone);
+#endif
+                    break;
+                }
+#if defined(MRT_EXPERIMENTS) && defined(MRT_WTIMES)
+                if (wt_f == 0) WT_MARK(wt_f);
+#endif
+                part_tries++;
+                part = (part + steal_step) % MRT_NPART;
+                in_tail = MRT_STEAL_SMALL;
+            }
+            *i = pool_index32(r, have, pool32_next, nb, ne);
+        } else {
+            *i = pool32_next + r;  // (r < c <= have)
+        }
+        pool_take32(c, have, nb, ne, &pool32_next, &pool32_end);
+        exhausted = part_tries >= MRT_STEAL_TRIES && pool32_next >= pool32_end;
 #if defined(MRT_EXPERIMENTS) && defined(MRT_WTIMES)
         if (exhausted && wt_ex == 0) WT_MARK(wt_ex);
 #endif
@@ -579,8 +653,8 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                         st_off = idx * 12u;
                         st_pend = true;
                     } else {
-                        // the same three words at the same address, idx * 12 as two shift-adds (no
-                        // quarter-rate 32-bit multiply per finished path)
+                        // the same three words at the same address, idx * 12 as two shift-adds (in the
+                        // multiply's place; profiles/r13_valu_cost.txt prices the two forms alike)
                         const f3 R = end_path(ps, lev, L);
                         uint32_t i4 = idx << 2;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -631,13 +705,20 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                         q_head = q_n = 0;
                         if (!exhausted) {
                             uint64_t i = 0;
-                            // (a Cornell walk kernel reads the refill's parameters here, not across the loop)
+                            // (a Cornell walk kernel reads the refill's parameters here, not across the loop,
+                            // and claims in 32 bits)
                             const PathParams& Q = kBox6Walk<F> ? kernarg_params() : P;
-                            cold_load();
-                            if constexpr (kBox6Walk<F>) claim(64u, lane, true, &i, &Q);
-                            else claim(64u, lane, true, &i);
-                            cold_store();
-                            const bool valid = i < Q.n_paths;
+                            uint32_t j = 0;
+                            if constexpr (kBox6Walk<F>) {
+                                cold_load32();
+                                claim32(64u, lane, &j, Q);
+                                cold_store32();
+                            } else {
+                                cold_load();
+                                claim(64u, lane, true, &i);
+                                cold_store();
+                            }
+                            const bool valid = kBox6Walk<F> ? j < Q.n_paths : i < Q.n_paths;
                             BSTATC(17, valid);
                             if (valid) {
                                 BSTAT(10);
@@ -646,9 +727,9 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                                 f3 o, dir;
                                 // the index as the 32-bit value it is (i < n_paths is known here, and
                                 // path_coords' conversion to double was made from all 64 bits)
-                                uint32_t i32 = (uint32_t)i;
+                                uint32_t i32 = kBox6Walk<F> ? j : (uint32_t)i;
 #if defined(__HIP_DEVICE_COMPILE__)
-                                asm volatile("" : "+v"(i32));
+                                if constexpr (!kBox6Walk<F>) asm volatile("" : "+v"(i32));
 #endif
                                 path_key_of(Q, i32, rng, &u, &v);
                                 camera_ray_args<kTimeWord>(Q.sc, rng, u, v, &o, &dir, &time);

@@ -158,6 +158,47 @@ static_assert(WaveLds{3, 2, 24, 9, 2, 13, false}.queue_at() + 13u * 64u == WaveL
 // one claim must cover a whole wave's idle lanes (the pool hands out at most 64 at once)
 static_assert(MRT_TAIL_BATCH >= 64u && MRT_BATCH >= MRT_TAIL_BATCH, "claims must be at least a wave wide");
 
+// A wave's pool of claimed paths in 32 bits (the Cornell walk kernels' refill): a launch's path
+// indices are below n_paths < 2^32, so the pool's bounds, a claim's bounds and a lane's index are
+// 32-bit values, compared and clamped on the scalar unit (gfx950 has no scalar 64-bit order compare:
+// on 64-bit values every one of these was a vector instruction on broadcast operands).  Only a
+// counter's answer is 64 bits wide: counters keep counting past their partition's end, a claim's
+// worth per wave that finds the partition handed out.  Written without sums that could wrap, and
+// checked against the 64-bit expressions on the host (tools/claim_check.cpp).
+//
+// (host and device alike, whichever backend the including unit builds)
+#define MRT_HDFN __host__ __device__ __forceinline__
+
+// The answer `got` of a partition's counter (its first dynamic path + the counter's old value)
+// against the partition's end: the claim [*nb, *ne), or false when the partition is handed out.
+MRT_HDFN bool pool_claim32(uint64_t got, uint32_t batch, uint32_t pe, uint32_t* nb, uint32_t* ne) {
+    const uint32_t lo = (uint32_t)got;
+    if ((uint32_t)(got >> 32) != 0u || lo >= pe) return false;
+    *nb = lo;
+    *ne = pe - lo <= batch ? pe : lo + batch;  // min(got + batch, pe)
+    return true;
+}
+// ... whether a claim that ends at ne leaves the partition inside its tail zone (small claims from here)
+MRT_HDFN bool pool_tail32(uint32_t pe, uint32_t ne, uint32_t tail_zone) { return pe - ne <= tail_zone / MRT_NPART; }
+// The path index of the lane of rank r < c among the c lanes that take one: from the `have` paths
+// left in the pool [pool_next, ..), then from the fresh claim [nb, ne) (nb = ne = 0: there is none);
+// ~0u, which is no path of any launch, where both run out.
+MRT_HDFN uint32_t pool_index32(uint32_t r, uint32_t have, uint32_t pool_next, uint32_t nb, uint32_t ne) {
+    if (r < have) return pool_next + r;
+    const uint32_t k = r - have;
+    return k < ne - nb ? nb + k : ~0u;
+}
+// ... and the pool once those c lanes are served (have < c: what is left of the fresh claim)
+MRT_HDFN void pool_take32(uint32_t c, uint32_t have, uint32_t nb, uint32_t ne, uint32_t* pool_next, uint32_t* pool_end) {
+    if (have < c) {
+        const uint32_t k = c - have;
+        *pool_next = k < ne - nb ? nb + k : ne;  // min(nb + k, ne)
+        *pool_end = ne;
+    } else {
+        *pool_next += c;
+    }
+}
+
 // kernel variants by scene features (the first instantiated superset is launched); FT_LIN
 // variants need the scene's linear hit program (mrt_lin.h), FT_ALL runs any graph.  The same list
 // in both numerics builds.
