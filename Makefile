@@ -17,7 +17,7 @@ CSRC     = miniraytracer_amd/csrc
 OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
-           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
+           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_cast.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
            $(OBJDIR)/mrt_temporal.o $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
@@ -69,6 +69,11 @@ $(OBJDIR)/mrt_tables.o: $(CSRC)/mrt_tables.hip $(HDRS)
 # the first-hit feature buffers (mrt_aux_kernel<F>): the exact contract's hit code in a translation
 # unit of its own, so the path-kernel objects above do not change with it
 $(OBJDIR)/mrt_aux.o: $(CSRC)/mrt_aux.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(HIPDEV) -DMRT_FAST=0 -c $< -o $@
+
+# the ray queries (mrt_cast_kernel<F>): the same, in a translation unit of its own
+$(OBJDIR)/mrt_cast.o: $(CSRC)/mrt_cast.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(HIPDEV) -DMRT_FAST=0 -c $< -o $@
 

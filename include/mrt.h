@@ -21,6 +21,8 @@
  *                                         uploaded                          camera.h:16-36
  *   mrt_reproject                         (new) carries a frame's samples into the next frame of a
  *                                         sequence; main() renders one still frame
+ *   mrt_cast_rays / mrt_cast_rays_device  scene.objects->hit(r, 0.001f, FLT_MAX, rec) for a caller's
+ *                                         own rays                          scene_object.h:22, main.cpp:71
  *
  * Threading: one host thread per device; calls on distinct scenes are thread-safe, calls on the
  * same scene handle are not reentrant.
@@ -372,6 +374,50 @@ mrt_status mrt_reproject_device(const float* d_rgb, const float* d_normal, const
                                 uint32_t height, const mrt_temporal_params* p, float* d_hist_out, void* stream);
         /* GPU; device frames (16-byte aligned), host cameras and params (read during the call, passed
            to the kernel by value); enqueued on `stream`, no sync, no allocation (capturable) */
+
+/* ---- ray queries ----------------------------------------------------------------------------------
+ * (an addition to this ABI; the reference's scene_object::hit is public to its callers,
+ * scene_object.h:22.)  The closest hit of caller rays against an uploaded scene, through the hit
+ * code the renders run: picking, focusing, visibility between two points, occlusion bakes.
+ *
+ * Ray i of a batch (i = 0 .. n-1):
+ *   the ray     ray(o, d, time, inside) (ray.h:18-56): d need not be of unit length, the constructor
+ *               normalises it (ray.h:30) and takes the direction mask from the argument (ray.h:51);
+ *               inside is 0 or 1 (dielectric.h's flag; anything non-zero counts as 1); reserved is
+ *               ignored.
+ *   the hit     objects->hit(r, 0.001f, FLT_MAX) (main.cpp:71): the render's own first-segment hit
+ *               under the exact numerics contract, the call the feature buffers make; tmin is the
+ *               reference's 0.001, fixed.
+ *   the stream  a constant_volume on the way (volumes.cpp:24) draws from
+ *               pcg32_srandom(seed + i, 4242) (uint64 wrap): a batch cut at k is two calls with
+ *               `seed` and `seed + k`.
+ *   a hit       when the closest hit exists and t <= tmax: hits[i] = (t, p, n, mat) -- t in units of
+ *               the normalised direction, n as hit_record::n holds it (not turned towards the ray),
+ *               mat the index into mrt_scene_view.materials.
+ *   otherwise   hits[i] = (+inf, 0,0,0, 0,0,0, MRT_NO_HIT), exactly those bits.  A tmax that is NaN
+ *               or <= 0.001 is a miss; tmax = +inf is the plain closest hit.
+ * No ray is rejected: a non-finite o or d yields what the reference's arithmetic yields, a miss
+ * included, and the call never faults.  Both backends return the same bits.
+ * n == 0: MRT_OK, nothing read, written or enqueued.  MRT_ERR_INVALID: a null pointer; a device
+ * pointer that is not 16-byte aligned; mrt_cast_rays_device on a CPU-backend scene. */
+typedef struct mrt_ray { float o[3], time; float d[3], tmax; uint32_t inside, reserved[3]; } mrt_ray;   /* 48 B */
+typedef struct mrt_hit { float t, p[3]; float n[3]; uint32_t mat; } mrt_hit;                           /* 32 B */
+#define MRT_NO_HIT 0xFFFFFFFFu
+/* Host records, both backends; returns when hits[] is written.  On a GPU scene it stages through
+ * device buffers of its own on a stream of its own and waits only for that work. */
+mrt_status mrt_cast_rays(mrt_scene* s, const mrt_ray* rays, uint32_t n, uint64_t seed, mrt_hit* hits);
+/* GPU backend only; device records.  Enqueued on `stream`: nothing is synchronised and nothing is
+ * allocated (capturable: a replay casts whatever d_rays then holds).  It reads the scene tables and
+ * d_rays and writes d_hits, nothing else -- nothing a render writes, so it may sit between two
+ * mrt_render_device calls on one stream without changing either -- and needs no mrt_prepare. */
+mrt_status mrt_cast_rays_device(mrt_scene* s, const mrt_ray* d_rays, uint32_t n, uint64_t seed, mrt_hit* d_hits, void* stream);
+/* The pinhole ray through the centre of pixel (x, y), row 0 = bottom, in the arithmetic of
+ * include/mrt_temporal.h step 2 (float32, no contraction, this order):
+ *   s = ((float)x + 0.5f) / (float)width, t = ((float)y + 0.5f) / (float)height
+ *   o = origin, d = ((llcorner + s horz) + t vert) - origin
+ *   time = cam->time0, tmax = +inf, inside = 0, reserved = 0
+ * MRT_ERR_INVALID: null, x >= width, y >= height, a zero size. */
+mrt_status mrt_camera_pixel_ray(const mrt_camera* cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, mrt_ray* out);
 
 /* ---- multi-GPU: the framebuffer gather over RCCL (xGMI) ---------------------------------------
  * The reference's seam is main.cpp:347-382 (the worker threads over one work_queue) writing

@@ -27,6 +27,42 @@ MAIN_SEED = 11350390909718046443  # main.cpp:302
 ASSET_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "assets")
 
 
+# mrt_ray / mrt_hit (include/mrt.h "ray queries"), byte for byte
+RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("time", "<f4"), ("d", "<f4", (3,)), ("tmax", "<f4"), ("inside", "<u4"), ("reserved", "<u4", (3,))])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("p", "<f4", (3,)), ("n", "<f4", (3,)), ("mat", "<u4")])
+NO_HIT = _lib.NO_HIT
+assert RAY_DTYPE.itemsize == 48 and HIT_DTYPE.itemsize == 32
+
+
+def _as_rays(rays):
+    """A contiguous RAY_DTYPE array from a RAY_DTYPE array or a float32 (n, 8) array of
+    o, time, d, tmax (inside = 0)."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError("rays: a RAY_DTYPE array or a float32 (n, 8) array of o, time, d, tmax")
+    out = np.zeros(a.shape[0], dtype=RAY_DTYPE)
+    out.view(np.float32).reshape(-1, 12)[:, :8] = a
+    return out
+
+
+def camera_pixel_rays(cam, width, height, xs, ys):
+    """mrt_camera_pixel_ray (include/mrt.h) for each (xs[k], ys[k]): the pinhole rays through those
+    pixel centres under the MrtCamera `cam` (row 0 = bottom), a RAY_DTYPE array with tmax = +inf."""
+    xs = np.asarray(xs, dtype=np.int64).reshape(-1)
+    ys = np.asarray(ys, dtype=np.int64).reshape(-1)
+    if xs.size != ys.size:
+        raise ValueError("camera_pixel_rays: xs and ys differ in length")
+    if ((xs < 0) | (ys < 0) | (xs >= 2 ** 32) | (ys >= 2 ** 32)).any():
+        raise ValueError("camera_pixel_rays: a pixel coordinate outside uint32")
+    out = np.zeros(xs.size, dtype=RAY_DTYPE)
+    fn, base = lib().mrt_camera_pixel_ray, out.ctypes.data
+    for k in range(xs.size):
+        check(fn(C.byref(cam), width, height, int(xs[k]), int(ys[k]), C.c_void_p(base + 48 * k)), "mrt_camera_pixel_ray")
+    return out
+
+
 def default_params():
     p = MrtParams()
     lib().mrt_default_params(C.byref(p))
@@ -193,6 +229,23 @@ class Renderer:
         """Enqueue the feature buffers into device memory (n_local float4 each, local_pixels order)."""
         check(lib().mrt_render_aux_device(self._h, C.byref(desc), C.c_void_p(d_normal_ptr), C.c_void_p(d_albedo_ptr),
                                           C.c_void_p(stream_ptr)), "mrt_render_aux_device")
+
+    def cast_rays(self, rays, seed=0):
+        """Closest hits of caller rays (include/mrt.h mrt_cast_rays), both backends: a HIT_DTYPE array,
+        one record per ray -- (t, p, n, mat), or (+inf, 0, 0, NO_HIT) for a miss or a hit past the ray's
+        tmax.  rays: a RAY_DTYPE array, or float32 (n, 8) rows of o, time, d, tmax (inside = 0).  Ray i
+        draws a volume's random numbers from the stream keyed by seed + i."""
+        r = _as_rays(rays)
+        hits = np.zeros(r.size, dtype=HIT_DTYPE)
+        check(lib().mrt_cast_rays(self._h, C.c_void_p(r.ctypes.data), r.size, C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_void_p(hits.ctypes.data)),
+              "mrt_cast_rays")
+        return hits
+
+    def cast_rays_device(self, d_rays_ptr, n, d_hits_ptr, seed=0, stream_ptr=0):
+        """The same on device records (torch data_ptr()s of n mrt_ray / n mrt_hit, 16-byte aligned),
+        enqueued on a HIP stream: nothing synchronised, nothing allocated (capturable)."""
+        check(lib().mrt_cast_rays_device(self._h, C.c_void_p(d_rays_ptr or None), n, C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                         C.c_void_p(d_hits_ptr or None), C.c_void_p(stream_ptr)), "mrt_cast_rays_device")
 
     def render_adaptive(self, desc, params=None, cancel=None):
         """Adaptive render (include/mrt.h mrt_render_adaptive), both backends: desc as the base pass, then

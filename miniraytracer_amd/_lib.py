@@ -23,6 +23,7 @@ RF_REF_ORDER = 0x10  # CPU backend: the reference's own RNG order (worker stream
 DEVICE_CPU = -1  # mrt_scene_upload device of the CPU backend (include/mrt.h MRT_DEVICE_CPU)
 ABI_VERSION = 6  # include/mrt.h MRT_ABI_VERSION: checked against mrt_abi_version() at load
 COMM_ID_BYTES = 128  # include/mrt.h MRT_COMM_ID_BYTES
+NO_HIT = 0xFFFFFFFF  # include/mrt.h MRT_NO_HIT: mrt_hit.mat of a miss
 
 
 class MrtParams(C.Structure):
@@ -222,6 +223,12 @@ def lib():
     L.mrt_reproject_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MrtCamera), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(MrtCamera), C.c_uint32, C.c_uint32, C.POINTER(MrtTemporalParams), C.c_void_p, C.c_void_p]
     L.mrt_reproject_device.restype = st
+    L.mrt_cast_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+    L.mrt_cast_rays.restype = st
+    L.mrt_cast_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.mrt_cast_rays_device.restype = st
+    L.mrt_camera_pixel_ray.argtypes = [C.POINTER(MrtCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.mrt_camera_pixel_ray.restype = st
     _lib = L
     return L
 
@@ -246,4 +253,5 @@ EXPORTS = [
     "mrt_moments", "mrt_moments_device", "mrt_moments_decide", "mrt_default_adaptive_params", "mrt_render_adaptive",
     "mrt_make_camera", "mrt_scene_camera_params", "mrt_scene_set_camera", "mrt_scene_set_camera_device",
     "mrt_default_temporal_params", "mrt_reproject", "mrt_reproject_device",
+    "mrt_cast_rays", "mrt_cast_rays_device", "mrt_camera_pixel_ray",
 ]

@@ -30,6 +30,12 @@
 // turns lookfrom about the vertical axis through lookat by k * DEG and uses the seed
 // splitmix64(seed + k); -temporal accumulates the frames (mrt_reproject, feature buffers at
 // min(spp, 16) samples); -denoise N then filters what is written, never the history.
+// -pick X Y casts the ray through the centre of pixel (X, Y), row 0 at the bottom (mrt_camera_pixel_ray,
+// mrt_cast_rays), under the final camera and prints "pick X Y: t=... p=(...) n=(...) mat=..." or
+// "pick X Y: miss" before the "Trace:" line.  -focusat X Y casts that pixel's ray under the camera the
+// other flags give and focuses the lens on what it hits: focus = t * -dot(d^, w) in float32, printed as
+// "focusat X Y: focus=..." (%.9g: -focus with that number renders the same image); a miss prints
+// "focusat X Y: miss" and leaves the focus alone.  With -frames it applies once, to frame 0's camera.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -208,6 +214,7 @@ int main(int argc, char** argv) {
     int lookfrom_i = 0, lookat_i = 0;
     double orbit_deg = 0.0;
     bool temporal = false, have_orbit = false;
+    int pick_xy[2] = {-1, -1}, focusat_xy[2] = {-1, -1};
     for (int i = 1; i < argc; i++) {
         const bool v1 = i + 1 < argc, v3 = i + 3 < argc;
         if (!strcmp(argv[i], "-temporal")) temporal = true;
@@ -217,6 +224,18 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "-aperture") && v1) aperture = argv[i + 1];
         if (!strcmp(argv[i], "-focus") && v1) focus = argv[i + 1];
         if (!strcmp(argv[i], "-frames") && v1) frames_s = argv[i + 1];
+        if (!strcmp(argv[i], "-pick") || !strcmp(argv[i], "-focusat")) {
+            int* at = argv[i][1] == 'p' ? pick_xy : focusat_xy;
+            char *e0 = nullptr, *e1 = nullptr;
+            const long x = i + 2 < argc ? strtol(argv[i + 1], &e0, 10) : -1, y = i + 2 < argc ? strtol(argv[i + 2], &e1, 10) : -1;
+            if (i + 2 >= argc || *e0 || *e1 || e0 == argv[i + 1] || e1 == argv[i + 2] || x < 0 || y < 0 || x >= (long)p.buffer_width ||
+                y >= (long)p.buffer_height) {
+                fprintf(stderr, "%s X Y: a pixel of the %u x %u image, row 0 at the bottom\n", argv[i], p.buffer_width, p.buffer_height);
+                return 1;
+            }
+            at[0] = (int)x;
+            at[1] = (int)y;
+        }
         if (!strcmp(argv[i], "-orbit") && v1) {
             orbit_deg = strtod(argv[i + 1], nullptr);
             have_orbit = true;
@@ -327,6 +346,39 @@ int main(int argc, char** argv) {
         if ((st = mrt_make_camera(&cp, &cam))) return fail("make_camera", st);
         for (int r = 0; r < world; r++)
             if ((st = mrt_scene_set_camera(scenes[r], &cam))) return fail("scene_set_camera", st);
+    }
+    // -focusat, then -pick: one ray through the pixel's centre under the camera as it stands
+    mrt_camera cam_now = view.camera;
+    if (have_cam && (st = mrt_make_camera(&cp, &cam_now))) return fail("make_camera", st);
+    auto cast_pixel = [&](const int* xy, mrt_ray* ray, mrt_hit* hit) {
+        mrt_status e = mrt_camera_pixel_ray(&cam_now, p.buffer_width, p.buffer_height, (uint32_t)xy[0], (uint32_t)xy[1], ray);
+        return e ? e : mrt_cast_rays(scenes[0], ray, 1, 0, hit);
+    };
+    if (focusat_xy[0] >= 0) {
+        mrt_ray ray;
+        mrt_hit hit;
+        if ((st = cast_pixel(focusat_xy, &ray, &hit))) return fail("focusat", st);
+        if (hit.mat == MRT_NO_HIT) {
+            printf("focusat %d %d: miss\n", focusat_xy[0], focusat_xy[1]);
+        } else {
+            // the hit's depth along the view axis: t * -dot(d^, w), float32
+            const float dl = sqrtf((ray.d[0] * ray.d[0] + ray.d[1] * ray.d[1]) + ray.d[2] * ray.d[2]);
+            const float dw = ((ray.d[0] / dl) * cam_now.w[0] + (ray.d[1] / dl) * cam_now.w[1]) + (ray.d[2] / dl) * cam_now.w[2];
+            cp.focus_dist = hit.t * -dw;
+            printf("focusat %d %d: focus=%.9g\n", focusat_xy[0], focusat_xy[1], (double)cp.focus_dist);
+            if ((st = mrt_make_camera(&cp, &cam_now))) return fail("make_camera", st);
+            for (int r = 0; r < world; r++)
+                if ((st = mrt_scene_set_camera(scenes[r], &cam_now))) return fail("scene_set_camera", st);
+        }
+    }
+    if (pick_xy[0] >= 0) {
+        mrt_ray ray;
+        mrt_hit hit;
+        if ((st = cast_pixel(pick_xy, &ray, &hit))) return fail("pick", st);
+        if (hit.mat == MRT_NO_HIT) printf("pick %d %d: miss\n", pick_xy[0], pick_xy[1]);
+        else
+            printf("pick %d %d: t=%.9g p=(%.9g %.9g %.9g) n=(%.9g %.9g %.9g) mat=%u\n", pick_xy[0], pick_xy[1], (double)hit.t, (double)hit.p[0],
+                   (double)hit.p[1], (double)hit.p[2], (double)hit.n[0], (double)hit.n[1], (double)hit.n[2], hit.mat);
     }
     if (frames_s) {
         if (have_adaptive || aux || (gather && !strcmp(gather, "rccl"))) {

@@ -12,6 +12,8 @@ void mrt_cpu_set_camera(mrt_cpu_scene* c, const mrt_camera* cam);
 mrt_status mrt_cpu_render(mrt_cpu_scene* c, const mrt_render_desc* d, float* rgb_out, uint64_t* rays_out, const volatile int* cancel);
 // first-hit feature buffers (mrt_render_aux): host W*H*4 each, owned pixels only
 mrt_status mrt_cpu_render_aux(mrt_cpu_scene* c, const mrt_render_desc* d, float* normal_out, float* albedo_out);
+// ray queries (mrt_cast_rays; arguments checked by the caller): host records
+mrt_status mrt_cpu_cast_rays(mrt_cpu_scene* c, const mrt_ray* rays, uint32_t n, uint64_t seed, mrt_hit* hits);
 // the adaptive render (mrt_render_adaptive; arguments checked by the caller)
 mrt_status mrt_cpu_render_adaptive(mrt_cpu_scene* c, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out, float* moments_out,
                                    uint64_t* rays_out, const volatile int* cancel);

@@ -41,6 +41,7 @@
 #include "mrt_cpu.h"
 #include "mrt_tables.h"
 #include "mrt_aux.h"
+#include "mrt_cast.h"
 #include "mrt_moments.h"
 #include "../../include/mrt_adaptive.h"
 
@@ -487,6 +488,40 @@ mrt_status mrt_cpu_render_aux(mrt_cpu_scene* c, const mrt_render_desc* d, float*
     };
     std::vector<std::thread> pool;
     for (uint32_t i = 1; i < n; i++) pool.emplace_back(work);
+    work();
+    for (std::thread& t : pool) t.join();
+    return MRT_OK;
+}
+
+// Ray queries (include/mrt.h mrt_cast_rays): mrt_cast_kernel's lane (mrt_cast.hip) over the batch --
+// per ray one cast_one (mrt_cast.h), its stream keyed by seed + i -- on worker threads that take 64
+// rays at a time.
+template <uint32_t F>
+static void cast_some(const mrt_cpu_scene* c, const mrt_ray* rays, uint32_t n, uint64_t seed, mrt_hit* hits, std::atomic<uint64_t>& next) {
+    Stacks st(c->T, 1);
+    const LStack Ls{st.frames.data(), st.rays.data(), st.mesh.data(), st.save.data(), 0u, nullptr, 0u};
+    for (;;) {
+        const uint64_t k0 = next.fetch_add(64, std::memory_order_relaxed);
+        if (k0 >= n) break;
+        for (uint64_t k = k0; k < std::min<uint64_t>(k0 + 64, n); k++) {
+            CastRay q;
+            memcpy(&q, rays + k, sizeof q);
+            const CastHit h = cast_one<F>(c->S, q, seed + k, Ls);
+            memcpy(hits + k, &h, sizeof h);
+        }
+    }
+}
+
+mrt_status mrt_cpu_cast_rays(mrt_cpu_scene* c, const mrt_ray* rays, uint32_t n, uint64_t seed, mrt_hit* hits) {
+    uint32_t nt = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    nt = (uint32_t)std::min<uint64_t>(nt, std::max<uint64_t>(((uint64_t)n + 1023) / 1024, 1));
+    std::atomic<uint64_t> next{0};
+    auto work = [&]() {
+        if (c->feats & FT_LIN) cast_some<F_LIN>(c, rays, n, seed, hits, next);
+        else cast_some<F_GEN>(c, rays, n, seed, hits, next);
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t i = 1; i < nt; i++) pool.emplace_back(work);
     work();
     for (std::thread& t : pool) t.join();
     return MRT_OK;

@@ -26,6 +26,7 @@
 #include "mrt_internal.h"
 #include "mrt_launch.h"
 #include "mrt_aux.h"
+#include "mrt_cast.h"
 #include "mrt_tables.h"
 #include "mrt_cpu.h"
 #include "mrt_moments.h"
@@ -432,6 +433,11 @@ struct mrt_scene {
     // its refinement passes' pixel lists come from mrt_internal_refine_slots over checked pixels (in
     // range, no repeats): mrt_prepare skips the list check (a sort) for them
     bool trust_pixels = false;
+    // the blocking mrt_cast_rays on a GPU scene: a stream and staging records of its own (rays, then
+    // hits), so the call waits for its own work only; kept until the scene is freed
+    hipStream_t cast_stream = nullptr;
+    void* d_cast = nullptr;
+    size_t d_cast_cap = 0;
 };
 
 // The LDS of a one-wave launch that only walks (the retrace and aux kernels): the generic machine's
@@ -655,6 +661,8 @@ extern "C" void mrt_scene_free(mrt_scene* s) {
     if (s->ev_aux_pending) (void)hipEventSynchronize(s->ev_aux);
     if (s->ev_aux) (void)hipEventDestroy(s->ev_aux);
     if (s->fstream) (void)hipStreamDestroy(s->fstream);
+    if (s->cast_stream) (void)hipStreamDestroy(s->cast_stream);
+    if (s->d_cast) (void)hipFree(s->d_cast);
     for (hipEvent_t e : {s->ev_kern, s->ev_fold[0], s->ev_fold[1]})
         if (e) (void)hipEventDestroy(e);
     delete s;  // (the workspace buffers release themselves: DevBuf)
@@ -1243,6 +1251,68 @@ extern "C" mrt_status mrt_render_aux(mrt_scene* s, const mrt_render_desc* d, flo
     for (size_t i = 0; i < px.size(); i++) {
         memcpy(normal_out + (size_t)px[i] * 4, &local[i * 4], 16);
         memcpy(albedo_out + (size_t)px[i] * 4, &local[(px.size() + i) * 4], 16);
+    }
+    return MRT_OK;
+}
+
+// ---- ray queries (include/mrt.h "ray queries") ----
+// One mrt_cast_kernel launch over device records: the scene's variant from the cast table, one-wave
+// groups with the exact build's walk stacks (the aux launch's).  It reads the scene tables and the
+// rays and writes the hits; nothing of the render workspace, so it needs no mrt_prepare, takes no
+// part in quiesce() and leaves no event behind.
+static mrt_status cast_launch(mrt_scene* s, const mrt_ray* d_rays, uint32_t n, uint64_t seed, mrt_hit* d_hits, hipStream_t q) {
+    CastParams P{};
+    P.sc = s->S;
+    P.rays = (const CastRay*)d_rays;
+    P.hits = (CastHit*)d_hits;
+    P.seed = seed;
+    P.n = n;
+    P.lds_frames = s->lds_frames;
+    P.lds_rays = s->lds_rays;
+    P.lds_mesh = s->lds_mesh;
+    P.lds_save = s->pl[0].lds_save;
+    const cast_kernel_t fn = cast_kernel_table().kernel[s->variant];
+    const size_t lds_bytes = walk_lds(s, P.lds_save).bytes();
+    hipLaunchKernelGGL(fn, dim3((uint32_t)(((uint64_t)n + 63u) / 64u)), dim3(64), lds_bytes, q, P);
+    HIPCHK(hipGetLastError());
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_cast_rays_device(mrt_scene* s, const mrt_ray* d_rays, uint32_t n, uint64_t seed, mrt_hit* d_hits, void* stream) {
+    MRT_GPU_ONLY(s, "mrt_cast_rays_device");
+    if (!s) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_cast_rays_device: null");
+    if (n == 0) return MRT_OK;
+    if (!d_rays || !d_hits) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_cast_rays_device: null");
+    if (((uintptr_t)d_rays | (uintptr_t)d_hits) & 15u) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_cast_rays_device: records not 16-byte aligned");
+    HIPCHK(hipSetDevice(s->device));
+    return cast_launch(s, d_rays, n, seed, d_hits, (hipStream_t)stream);
+}
+
+extern "C" mrt_status mrt_cast_rays(mrt_scene* s, const mrt_ray* rays, uint32_t n, uint64_t seed, mrt_hit* hits) {
+    if (!s) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_cast_rays: null");
+    if (n == 0) return MRT_OK;
+    if (!rays || !hits) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_cast_rays: null");
+    if (s->cpu) return mrt_cpu_cast_rays(s->cpu, rays, n, seed, hits);
+    HIPCHK(hipSetDevice(s->device));
+    // staged in pieces of at most 2^20 rays (80 MiB of device records); piece k0 casts with seed + k0
+    const uint32_t piece = std::min(n, 1u << 20);
+    if (!s->cast_stream) HIPCHK(hipStreamCreateWithFlags(&s->cast_stream, hipStreamNonBlocking));
+    const size_t need = (size_t)piece * (sizeof(mrt_ray) + sizeof(mrt_hit));
+    if (s->d_cast_cap < need) {
+        if (s->d_cast) (void)hipFree(s->d_cast);
+        s->d_cast = nullptr;
+        s->d_cast_cap = 0;
+        if (hipMalloc(&s->d_cast, need) != hipSuccess) return mrt_internal_fail(MRT_ERR_OOM, "mrt_cast_rays: device records");
+        s->d_cast_cap = need;
+    }
+    mrt_ray* const d_rays = (mrt_ray*)s->d_cast;
+    mrt_hit* const d_hits = (mrt_hit*)((char*)s->d_cast + (size_t)piece * sizeof(mrt_ray));  // (48 * piece: 16-byte aligned)
+    for (uint64_t k0 = 0; k0 < n; k0 += piece) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - k0);
+        HIPCHK(hipMemcpyAsync(d_rays, rays + k0, (size_t)m * sizeof(mrt_ray), hipMemcpyHostToDevice, s->cast_stream));
+        if (mrt_status st = cast_launch(s, d_rays, m, seed + k0, d_hits, s->cast_stream)) return st;
+        HIPCHK(hipMemcpyAsync(hits + k0, d_hits, (size_t)m * sizeof(mrt_hit), hipMemcpyDeviceToHost, s->cast_stream));
+        HIPCHK(hipStreamSynchronize(s->cast_stream));
     }
     return MRT_OK;
 }
