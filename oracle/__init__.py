@@ -24,7 +24,8 @@ REF_DIR = os.path.join(HERE, "_ref")
 class OracleDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("sqrt_samples", C.c_uint32),
                 ("max_bounces", C.c_uint32), ("max_luminance", C.c_float), ("mode", C.c_uint32),
-                ("seed", C.c_uint64), ("threads", C.c_uint32), ("y0", C.c_uint32), ("y1", C.c_uint32)]
+                ("seed", C.c_uint64), ("threads", C.c_uint32), ("y0", C.c_uint32), ("y1", C.c_uint32),
+                ("fold", C.c_uint32)]
 
 
 _lib = None
@@ -53,9 +54,12 @@ def lib():
 
 
 def desc(width, height, samples, depth=32, max_luminance=1000.0, mode=0, seed=11350390909718046443, threads=1,
-         y0=0, y1=0):
+         y0=0, y1=0, fold=0):
+    """fold=0: the reference's deepest-first fold of a path's levels; fold=1: the forward fold (a
+    throughput multiplied level by level, oracle_desc.fold) -- what the tolerance contract's
+    path-exact kernels compute."""
     sq = int(np.sqrt(np.float32(samples)))
-    return OracleDesc(width, height, sq, depth, max_luminance, mode, seed, threads, y0, y1)
+    return OracleDesc(width, height, sq, depth, max_luminance, mode, seed, threads, y0, y1, fold)
 
 
 def render(scene, d, paths=False):
@@ -69,10 +73,19 @@ def render(scene, d, paths=False):
     return img, rays, prgb, prays
 
 
+def path(scene, d, x, y, s):
+    """One path (pixel (x, y), row 0 = bottom; sample s) of the render `d`: (radiance [3], rays)."""
+    out = np.zeros(3, dtype=np.float32)
+    rays = lib().oracle_path(C.byref(scene.view), C.byref(d), int(x), int(y), int(s), out.ctypes.data)
+    return out, int(rays)
+
+
 def render_ref_order(scene, d, tile_size=32):
     """The reference's own deterministic mode (-threads 1): one worker stream seeded as main() seeds
     worker 0 (main.cpp:357-361), work_queue tile order, draw() (mode 0) / draw2() (mode 1).
     Returns (image [H, W, 4], rays)."""
+    if d.fold != 0:
+        raise ValueError("render_ref_order: the reference's own order has the reference's own fold (fold=0)")
     img = np.zeros((d.height, d.width, 4), dtype=np.float32)
     st, sq = scene.worker_seeds(1)[0]
     rays = lib().oracle_render_ref_order(C.byref(scene.view), C.byref(d), tile_size, st, sq, img.ctypes.data)

@@ -508,7 +508,19 @@ static V obj_pdf_generate(ctx* C, uint32_t id, V origin, float time) {
 }
 
 /* ---------------------------------------------------------------- trace (main.cpp:66-118) */
-typedef struct { uint32_t max_bounces; uint64_t rays; } tstate;
+/* fwd (oracle_desc.fold = 1): the forward fold.  thr is the path's throughput so far, (1,1,1) at
+ * the camera; a scattering level multiplies it and traces on, and the path's end returns
+ * thr * L_end.  fwd = 0 is the reference's recursion, untouched. */
+typedef struct { uint32_t max_bounces; uint64_t rays; int fwd; V thr; } tstate;
+static tstate tstate_of(const oracle_desc* d) {
+    tstate T;
+    T.max_bounces = d->max_bounces;
+    T.rays = 0;
+    T.fwd = d->fold != 0;
+    T.thr = v3(1.0f, 1.0f, 1.0f);
+    return T;
+}
+static V path_end(const tstate* T, V L) { return T->fwd ? vmul(T->thr, L) : L; }
 
 static V trace(ctx* C, tstate* T, const ray* r, uint32_t depth) {
     const mrt_scene_view* v = C->v;
@@ -525,6 +537,10 @@ static V trace(ctx* C, tstate* T, const ray* r, uint32_t depth) {
                 V reflected = vsub(r->dir, vscale(dp, hrec.n));
                 ray sr = mkray(hrec.p, vadd(reflected, vscale(1 - M->p, random_in_sphere(&C->rng))), r->time, 0);
                 V att = tex_sample(v, M->tex, hrec.u, hrec.v, hrec.p);
+                if (T->fwd) {
+                    T->thr = vmul(T->thr, att);
+                    return trace(C, T, &sr, depth + 1);
+                }
                 return vmul(att, trace(C, T, &sr, depth + 1));
             }
             if (M->kind == MRT_M_DIELECTRIC) { /* material.h:121-175 */
@@ -566,6 +582,7 @@ static V trace(ctx* C, tstate* T, const ray* r, uint32_t depth) {
                 } else {
                     sr = mkray(hrec.p, reflected, r->time, r->inside);
                 }
+                if (T->fwd) return trace(C, T, &sr, depth + 1);
                 return vmul(v3(1.0f, 1.0f, 1.0f), trace(C, T, &sr, depth + 1));
             }
             /* lambertian / isotropic + mix_pdf (main.cpp:84-102) */
@@ -596,18 +613,23 @@ static V trace(ctx* C, tstate* T, const ray* r, uint32_t depth) {
             } else {
                 spdf = 1.0f / (2.0f * PI_F);
             }
+            if (T->fwd) {
+                V af = vscale(spdf, att);
+                T->thr = vdivf(vmul(T->thr, af), pdf_v);
+                return trace(C, T, &scattered, depth + 1);
+            }
             V col = trace(C, T, &scattered, depth + 1);
             V a = vscale(spdf, att);
             V x = vmul(a, col);
             return vadd(emitted, vdivf(x, pdf_v));
         }
-        return emitted;
+        return path_end(T, emitted);
     }
     if (v->sky) {
         float t = 0.5f * (r->dir.y + 1.0f);
-        return vadd(v3(1.0f - t, 1.0f - t, 1.0f - t), vscale(t, v3(0.5f, 0.7f, 1.0f)));
+        return path_end(T, vadd(v3(1.0f - t, 1.0f - t, 1.0f - t), vscale(t, v3(0.5f, 0.7f, 1.0f))));
     }
-    return v3(0, 0, 0);
+    return path_end(T, v3(0, 0, 0));
 }
 
 /* camera::get_ray (camera.h:38-44) */
@@ -628,7 +650,7 @@ static V path_with(ctx* C, const oracle_desc* d, uint32_t x, uint32_t y, uint32_
     float u = (x + dx) / (float)d->width;
     float vv = (y + dy) / (float)d->height;
     ray r = get_ray(C, u, vv);
-    tstate T = {d->max_bounces, 0};
+    tstate T = tstate_of(d);
     V c = trace(C, &T, &r, 0);
     *rays = (uint32_t)T.rays;
     return c;
@@ -645,7 +667,7 @@ static V one_path(const mrt_scene_view* v, const oracle_desc* d, uint32_t x, uin
     float u = (x + dx) / (float)d->width;
     float vv = (y + dy) / (float)d->height;
     ray r = get_ray(&C, u, vv);
-    tstate T = {d->max_bounces, 0};
+    tstate T = tstate_of(d);
     V c = trace(&C, &T, &r, 0);
     *rays = (uint32_t)T.rays;
     return c;
@@ -796,6 +818,7 @@ static uint32_t work_tiles(uint32_t W, uint32_t H, uint32_t ts, otile** out) {
 
 uint64_t oracle_render_ref_order(const mrt_scene_view* v, const oracle_desc* d, uint32_t tile_size, uint64_t initstate, uint64_t initseq,
                                  float* rgb) {
+    if (d->fold != 0) return UINT64_MAX;
     ctx C;
     C.v = v;
     pcg_srandom(&C.rng, initstate, initseq); /* Init_Thread_RNG(args.initstate, args.initseq), main.cpp:143/198 */

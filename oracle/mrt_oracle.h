@@ -25,6 +25,13 @@ typedef struct oracle_desc {
     uint64_t seed;   /* stream key seed */
     uint32_t threads;
     uint32_t y0, y1; /* row range to render (y1 = 0: all rows) */
+    /* 0: each path folds its levels deepest-first, as trace()'s recursion returns (the reference).
+     * 1: forward fold -- a throughput T = (1,1,1) is multiplied level by level on the way down
+     *    (metal T = T*att; dielectric unchanged; lambertian / isotropic a = spdf*att, T = (T*a)/pdf)
+     *    and the path returns T * L_end (the light's emission, the sky, or black).  Same geometry,
+     *    draws and ray counts; only the rounding of the product differs.  oracle_render and
+     *    oracle_path honour it, oracle_render_ref_order refuses it. */
+    uint32_t fold;
 } oracle_desc;
 
 /* Render rows [y0,y1) of the image into rgb (W*H*4 floats, row 0 = bottom); optional per-path
@@ -35,7 +42,8 @@ uint64_t oracle_render(const mrt_scene_view* v, const oracle_desc* d, float* rgb
  * (initstate, initseq) = the worker seeds main() draws after select_scene (main.cpp:357-361, see
  * mrt_worker_seeds), tiles of tile_size in work_queue order; mode 0 = draw() over work_queue_seq
  * (tile -> row -> pixel -> sample), mode 1 = draw2() over work_queue_dynamic (sample-major passes
- * over the tiles).  rgb = W*H*4 floats (row 0 = bottom).  Returns G_rayCounter. */
+ * over the tiles).  rgb = W*H*4 floats (row 0 = bottom).  Returns G_rayCounter, or UINT64_MAX
+ * (nothing rendered) for d->fold != 0: the reference's own order has the reference's own fold. */
 uint64_t oracle_render_ref_order(const mrt_scene_view* v, const oracle_desc* d, uint32_t tile_size, uint64_t initstate, uint64_t initseq,
                                  float* rgb);
 

@@ -11,7 +11,9 @@ host leg (no GPU)  the CPU backend equals the C restatement bit for bit (image, 
 GPU leg            the kernel picked is the entry's literal; the exact contract equals the
                    restatement per path (radiance bits, ray counts), also under the test hooks that
                    force the other walks; the tolerance contract holds the bars
-                   test_fast_numerics_close_to_exact_other_scenes uses.
+                   test_fast_numerics_close_to_exact_other_scenes uses, and where it runs the path-exact
+                   build it equals the restatement's forward fold (oracle.desc(fold=1)) per path, again
+                   under the hooks whose walk runs that build.
 
 The feature / kernel literals are worked out by hand from scene_features (mrt_tables.hip) and
 pick_variant (mrt_render.hip, mrt_launch.h kVariants): index 0-2 the shape-specialised walks, 3-7 the narrower
@@ -605,9 +607,9 @@ def launch_size(ki):
     return 128, 64
 
 
-def assert_exact(mrt, r, e, w, spp, ref, what):
+def assert_exact(mrt, r, e, w, spp, ref, what, numerics="exact"):
     oimg, orays, prgb, prays = ref
-    d = mrt.render_desc(w, w, spp, depth=e.depth, mode=e.mode, flags=mrt._lib.RF_PATH_DEBUG)
+    d = mrt.render_desc(w, w, spp, depth=e.depth, mode=e.mode, numerics=numerics, flags=mrt._lib.RF_PATH_DEBUG)
     img, rays = r.render(d)
     grgb, grays = gpu_paths(mrt, r, d)
     print(f"{e.name} [{what}]: {w}x{w}x{spp}: GPU rays {rays}, restatement rays {orays}")
@@ -667,4 +669,20 @@ def test_gpu_equals_restatement(gpu, orc, e, monkeypatch):
         assert rmse < 0.05
         if e.fast == "pex":  # the path-exact build: "the paths are the same" 
             assert frays == ref64[1]
+            # ... and each one's radiance is the forward fold of the same levels: per path, per pixel and
+            # in the ray total the build equals the restatement's forward fold bit for bit, through
+            # every walk of the entry's hooks that runs it
+            fwd = orc.render(s, orc.desc(w, w, 64, depth=e.depth, mode=e.mode, threads=16, fold=1), paths=True)
+            assert_exact(mrt, r, e, w, 64, fwd, "pex", numerics="fast")
+            assert mrt._lib.BUILDS[r.kernel_info()["build"]] == "pex"
+            for hook in e.hooks:
+                with monkeypatch.context() as mp:
+                    mp.setenv(hook, "1")
+                    rh = mrt.Renderer(s, 0)
+                rh.render(mrt.render_desc(16, 16, 1, depth=e.depth, mode=e.mode, numerics="fast"))
+                build = mrt._lib.BUILDS[rh.kernel_info()["build"]]
+                print(f"{e.name} [fast, {hook}]: build {build}")
+                if build == "pex":
+                    assert_exact(mrt, rh, e, w, 64, fwd, f"pex {hook}", numerics="fast")
+                rh.close()
     r.close()
