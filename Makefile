@@ -110,7 +110,7 @@ bin/mrt: $(CSRC)/mrt_cli.cpp miniraytracer_amd/libmrt.so include/mrt.h
 	@mkdir -p bin
 	$(HIPCC) -O2 -std=c++17 -ffp-contract=off $(CSRC)/mrt_cli.cpp -Lminiraytracer_amd -lmrt -Wl,-rpath,'$$ORIGIN/../miniraytracer_amd' -o $@
 
-oracle/liboracle.so: oracle/mrt_oracle.c oracle/mrt_oracle.h include/mrt_scene.h
+oracle/liboracle.so: oracle/mrt_oracle.c oracle/mrt_oracle.h include/mrt_scene.h include/mrt_mathfn.h
 	$(CC) -O2 -std=c11 -fPIC -shared -ffp-contract=off -fno-fast-math $(HOSTFMA) -Wall -o $@ oracle/mrt_oracle.c -lm -lpthread
 
 # The scene compiler stand-alone on the CPU under AddressSanitizer + UBSan (host code only, nothing

@@ -74,10 +74,11 @@ MRT_HD void mrt_sincos_d(double x, double* s, double* c) {
     *s = (n & 2) ? -ss : ss;
     *c = ((n + 1) & 2) ? -cc : cc;
 }
+/* (sin and tan of -0 are -0, as IEEE has them: the reduction's r = x - k pi/2 turns -0 into +0) */
 MRT_HD float mrt_sinf(float x) {
     double s, c;
     mrt_sincos_d((double)x, &s, &c);
-    return (float)s;
+    return x == 0.0f ? x : (float)s;
 }
 MRT_HD float mrt_cosf(float x) {
     double s, c;
@@ -87,7 +88,7 @@ MRT_HD float mrt_cosf(float x) {
 MRT_HD float mrt_tanf(float x) {
     double s, c;
     mrt_sincos_d((double)x, &s, &c);
-    return (float)(s / c);
+    return x == 0.0f ? x : (float)(s / c);
 }
 
 /* ---- log: x = m 2^e, m in [sqrt(1/2), sqrt(2)), log m = 2 atanh((m-1)/(m+1)) ---- */

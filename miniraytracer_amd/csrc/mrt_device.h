@@ -244,7 +244,13 @@ MRT_DFN f3 normalize(f3 a) {
     f3 q{div_core(a.x, len, y), div_core(a.y, len, y), div_core(a.z, len, y)};
     const uint32_t mn = min(min(mag2(a.x) - 1u, mag2(a.y) - 1u), mag2(a.z) - 1u);  // 0 -> UINT_MAX
     const bool ok = MRT_MAG_IN(dd, -52, 52) & (mn >= MRT_MAG2(-100) - 1u);
-    if (__builtin_expect(any_lane(!ok), 0)) q = ok ? q : divf(a, __builtin_sqrtf(dd));
+    // A per-lane branch, not `any_lane(!ok)` and a select: inside mesh_leaf (a divergent region: only
+    // the lanes whose leaf hit) the wave-uniform branch on the ballot was left unstructurised
+    // (-structurizecfg-skip-uniform-regions), and the compiler rebuilt the lane mask of the leaf's
+    // `has` on that path as a constant for the whole wave -- every lane of the wave then counted as a
+    // mesh hit, with an unwritten record (mrt_cast_kernel<room + mesh>; tests/test_edge_rays_gpu.py
+    // test_device_degenerate_mesh_normals).  The divergent branch is structurised like any other.
+    if (__builtin_expect(!ok, 0)) q = divf(a, __builtin_sqrtf(dd));
     return q;
 }
 MRT_DFN f3 cross(f3 a, f3 b) { return f3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
@@ -409,8 +415,10 @@ MRT_DFN bool ray_nice(f3 o, f3 d) {
     if (MRT_FAST_GUARDS) return true;  // no exactness guards: every ray takes the hardware reciprocal
     const bool dn = MRT_MAG_IN(d.x, -26, 1) & MRT_MAG_IN(d.y, -26, 1) & MRT_MAG_IN(d.z, -26, 1);
     const uint32_t mn = min(min(mag2(o.x) - 1u, mag2(o.y) - 1u), mag2(o.z) - 1u);  // 0 -> UINT_MAX
-    const float mx = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-    return dn & (mn >= MRT_MAG2(-77) - 1u) & (mx <= 0x1p60f);
+    // (the largest magnitude by its key, not by fmaxf, which drops a NaN: a NaN origin component is
+    // above every finite key and not nice -- its slab values are NaN, aabb_hit_b's slow path)
+    const uint32_t mx = max(max(mag2(o.x), mag2(o.y)), mag2(o.z));
+    return dn & (mn >= MRT_MAG2(-77) - 1u) & (mx <= MRT_MAG2(60));
 }
 // 1/d per component (aabb.h:49), exact
 MRT_DFN f3 ray_inv(f3 d, bool nice) {

@@ -49,6 +49,8 @@ def lib():
         L.oracle_samplers.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
         L.oracle_pdf.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                  C.c_void_p]
+        L.oracle_mathfn.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_mathfn.restype = None
         _lib = L
     return _lib
 
@@ -109,6 +111,19 @@ def pcg_stream(st, sq, n):
 def samplers(st, sq, n, which):
     out = np.zeros((n, 3), dtype=np.float32)
     lib().oracle_samplers(st, sq, n, which, out.ctypes.data)
+    return out
+
+
+MATHFN = ("sin", "cos", "tan", "log", "log10", "asin", "exp", "pow5", "atan2", "pow")
+
+
+def mathfn(name, a, b=None):
+    """include/mrt_mathfn.h's float function `name` of MATHFN over float32 arrays (atan2(a, b), pow(a, b))."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(a if b is None else b, dtype=np.float32)
+    assert a.shape == b.shape
+    out = np.zeros(a.shape, dtype=np.float32)
+    lib().oracle_mathfn(MATHFN.index(name), a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data)
     return out
 
 

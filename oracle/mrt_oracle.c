@@ -922,3 +922,23 @@ void oracle_pdf(const mrt_scene_view* v, uint32_t id, uint32_t n, const float* i
         next[i] = pcg_next(&C.rng);
     }
 }
+
+/* The transcendentals of include/mrt_mathfn.h as array calls (tests/test_mathfn_host.py).  which: 0 sin,
+ * 1 cos, 2 tan, 3 log, 4 log10, 5 asin, 6 exp, 7 pow5 (out[i] = f(a[i]); b unused), 8 atan2(a[i], b[i]),
+ * 9 pow(a[i], b[i]). */
+void oracle_mathfn(uint32_t which, uint32_t n, const float* a, const float* b, float* out) {
+    for (uint32_t i = 0; i < n; i++) {
+        switch (which) {
+        case 0: out[i] = mrt_sinf(a[i]); break;
+        case 1: out[i] = mrt_cosf(a[i]); break;
+        case 2: out[i] = mrt_tanf(a[i]); break;
+        case 3: out[i] = mrt_logf(a[i]); break;
+        case 4: out[i] = mrt_log10f(a[i]); break;
+        case 5: out[i] = mrt_asinf(a[i]); break;
+        case 6: out[i] = mrt_expf(a[i]); break;
+        case 7: out[i] = mrt_pow5f(a[i]); break;
+        case 8: out[i] = mrt_atan2f(a[i], b[i]); break;
+        default: out[i] = mrt_powf(a[i], b[i]); break;
+        }
+    }
+}

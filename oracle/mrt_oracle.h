@@ -57,6 +57,9 @@ int oracle_hit(const mrt_scene_view* v, const float* o, const float* dir, float 
 /* PCG KAT helpers */
 void oracle_pcg_stream(uint64_t initstate, uint64_t initseq, uint32_t n, uint32_t* out);
 void oracle_samplers(uint64_t initstate, uint64_t initseq, uint32_t n, uint32_t which, float* out /* n*3 */);
+/* include/mrt_mathfn.h as array calls: which 0 sin, 1 cos, 2 tan, 3 log, 4 log10, 5 asin, 6 exp, 7 pow5
+ * (of a[i]), 8 atan2(a[i], b[i]), 9 pow(a[i], b[i]) */
+void oracle_mathfn(uint32_t which, uint32_t n, const float* a, const float* b, float* out);
 
 #ifdef __cplusplus
 }

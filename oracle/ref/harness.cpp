@@ -17,7 +17,9 @@
 //   --h-mode scene     dump the scene graph select_scene() builds (types, parameters as float
 //                      bits, BVH topology incl. node_order) and the camera.
 //   --h-mode pdf       object pdf KATs: pdf_value / pdf_generate of spheres, rects and object_lists.
-//   --h-mode hits      closest-hit KATs: seeded random rays against scene.objects->hit().
+//   --h-mode hits      closest-hit KATs: seeded random rays against scene.objects->hit(); with
+//                      --h-rays FILE the rays are read from FILE instead (raw float32, n x 8: o, d,
+//                      time, inside as int32 bits) and none is drawn.
 //
 // The reference's platform layer (SDL / GDI) is not compiled; the MRT_* entry points declared in
 // platform.h:4-19 are implemented below as a headless driver.  With -DMRT_MATHMATCH the float
@@ -446,22 +448,41 @@ static int mode_hits(int argc, char** argv) {
     scene sc = harness_select_scene((scenes)p->sceneSelect, float(p->bufferWidth) / float(p->bufferHeight));
     int n = atoi(harg(argc, argv, "--h-n", "4096"));
     const char* out = harg(argc, argv, "--h-out", "hits.npy");
+    // --h-rays FILE: the caller's rays, n x 8 float32 (o, d, time, inside); n is the file's row count
+    const char* rays_file = harg(argc, argv, "--h-rays", "");
+    std::vector<float> given;
+    if (rays_file[0]) {
+        FILE* f = fopen(rays_file, "rb");
+        if (!f) { fprintf(stderr, "--h-rays: cannot open %s\n", rays_file); return 2; }
+        float row[8];
+        while (fread(row, sizeof(float), 8, f) == 8) given.insert(given.end(), row, row + 8);
+        fclose(f);
+        n = (int)(given.size() / 8);
+    }
     // rays: camera rays at random (u,v) then one random continuation from the hit point
     std::vector<float> rec((size_t)n * 16, 0.f);
     for (int i = 0; i < n; i++) {
-        Init_Thread_RNG(1234567 + (uint64_t)i, 7654321);  // ray generation stream
         float* r = &rec[(size_t)i * 16];
         Vec3 o, d;
         float tm;
         int ins = 0;
-        if (i % 2 == 0) {
-            ray cr = sc.camera->get_ray(randf(), randf());
-            o = cr.origin; d = cr.dir; tm = cr.time;
+        if (rays_file[0]) {
+            const float* g = &given[(size_t)i * 8];
+            o = Vec3(g[0], g[1], g[2]);
+            d = Vec3(g[3], g[4], g[5]);
+            tm = g[6];
+            memcpy(&ins, &g[7], 4);
         } else {
-            o = Vec3(randf() * 555.f, randf() * 555.f, randf() * 555.f);
-            d = random_in_sphere();
-            tm = randf();
-            ins = (i % 6 == 1);
+            Init_Thread_RNG(1234567 + (uint64_t)i, 7654321);  // ray generation stream
+            if (i % 2 == 0) {
+                ray cr = sc.camera->get_ray(randf(), randf());
+                o = cr.origin; d = cr.dir; tm = cr.time;
+            } else {
+                o = Vec3(randf() * 555.f, randf() * 555.f, randf() * 555.f);
+                d = random_in_sphere();
+                tm = randf();
+                ins = (i % 6 == 1);
+            }
         }
         ray rr(o, d, tm, ins);
         hit_record h;

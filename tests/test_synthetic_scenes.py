@@ -73,22 +73,29 @@ def b_cornell_plus_sphere(mrt):
     return s, base
 
 
-def lookalike(mrt, closed=True, with_box=True):
+def lookalike(mrt, closed=True, with_box=True, scale=1.0, planes=0.0, glass=False):
     """SIG_CORNELL's op / kind / skip sequence on other numbers: a room of 100 units, a box of another
-    shape under a negative angle, a lambertian sphere elsewhere, the light moved and resized."""
+    shape under a negative angle, a lambertian sphere elsewhere, the light moved and resized.
+    scale: every coordinate and the camera times it (a power of two); planes: the plane of the floor and
+    of the left wall (0: ordinary; off zero and below 2^-77 they are MRT_F_SLOWDIV rects); glass: a
+    dielectric sphere in place of the lambertian one."""
     s = Synth(ref_scene(mrt, 5)).clear()
-    s.scale_camera(100.0 / 555.0)
+    s.scale_camera(100.0 / 555.0 * scale)
     red, white, green = s.lambertian(0.6, 0.1, 0.1), s.lambertian(0.7, 0.7, 0.6), s.lambertian(0.1, 0.5, 0.2)
     light = s.material(ss.M_LIGHT, s.color(11, 12, 13), 1.0)
-    L = 100.0
-    lamp = s.rect(ss.K_XZ, 30, 62, 41, 73, 99.5, light, -1.0)
-    walls = [s.rect(ss.K_YZ, 0, L, 0, L, L, green, -1.0), s.rect(ss.K_YZ, 0, L, 0, L, 0, red, 1.0), lamp,
-             s.rect(ss.K_XZ, 0, L, 0, L, L, white, -1.0), s.rect(ss.K_XZ, 0, L, 0, L, 0, white, 1.0),
-             s.rect(ss.K_XY, 0, L, 0, L, L if closed else 90.0, white, -1.0)]
-    box = s.translate(s.rotate_y(s.box((0, 0, 0), (28, 55, 31), white), -18.0, box=(-40, 0, -40, 60, 56, 60)), (52, 0, 47))
-    ball = s.sphere((27, 15, 30), 15, s.lambertian(0.3, 0.3, 0.8))
-    s.root = s.list(walls + ([box] if with_box else []) + [ball], box=(-1, -1, -1, 101, 101, 101))
-    s.biased = s.list([lamp], box=(30, 99, 41, 62, 100, 73))
+
+    def c(*v):
+        return [x * scale for x in v]
+
+    L = 100.0 * scale
+    lamp = s.rect(ss.K_XZ, *c(30, 62, 41, 73, 99.5), light, -1.0)
+    walls = [s.rect(ss.K_YZ, 0, L, 0, L, L, green, -1.0), s.rect(ss.K_YZ, 0, L, 0, L, planes, red, 1.0), lamp,
+             s.rect(ss.K_XZ, 0, L, 0, L, L, white, -1.0), s.rect(ss.K_XZ, 0, L, 0, L, planes, white, 1.0),
+             s.rect(ss.K_XY, 0, L, 0, L, L if closed else 90.0 * scale, white, -1.0)]
+    box = s.translate(s.rotate_y(s.box((0, 0, 0), c(28, 55, 31), white), -18.0, box=c(-40, 0, -40, 60, 56, 60)), c(52, 0, 47))
+    ball = s.sphere(c(27, 15, 30), 15 * scale, s.material(ss.M_DIELECTRIC, ss.NONE, 1.5) if glass else s.lambertian(0.3, 0.3, 0.8))
+    s.root = s.list(walls + ([box] if with_box else []) + [ball], box=c(-1, -1, -1, 101, 101, 101))
+    s.biased = s.list([lamp], box=c(30, 99, 41, 62, 100, 73))
     return s
 
 
@@ -138,6 +145,40 @@ def b_mesh_degenerate(mrt):
     s.tri_geo[np.argsort(area)[-2:], 4:8] = 0.0
     s._view = None
     return s, base
+
+
+def degenerate_normals(mrt):
+    """The room + mesh lookalike whose vertex normals sum to 0, to ~1e-30 and to ~1e25 on a quarter of
+    the triangles each: mesh_leaf's normalize takes its IEEE fallback (|n|^2 out of [2^-52, 2^52))."""
+    s = room_mesh_lookalike(mrt, False)
+    n = s.tri_nrm.copy()
+    k = np.arange(len(n))
+    n[k % 4 == 0] = 0.0
+    n[k % 4 == 1] *= np.float32(1e-30)
+    n[k % 4 == 2] *= np.float32(1e25)
+    s.set_mesh(s.mesh_nodes, s.tri_geo, n)
+    return s
+
+
+def scaled_spheres(s, k):
+    """A graph of spheres, lists and bvh_nodes (and its camera) scaled by k about the origin."""
+    s = s.copy()
+    k = np.float32(k)
+    kind = s.nodes["kind"] & 0xFF
+    f = s.nodes["f"]
+    assert set(int(x) for x in kind) <= {ss.K_SPHERE, ss.K_LIST, ss.K_BVH}
+    sp = kind == ss.K_SPHERE
+    f[sp, 0:6] *= k
+    f[sp, 8] *= k
+    f[~sp, 0:6] *= k
+    s.scale_camera(k)
+    s._view = None
+    return s
+
+
+def b_tree_scaled(mrt):
+    s, _ = b_tree_list_leaves(mrt)
+    return scaled_spheres(s, 2.0 ** 50), s
 
 
 def room_mesh_lookalike(mrt, metal):
@@ -493,6 +534,28 @@ CATALOGUE = [
     Entry("r_room_2_walls_is_no_room", lambda m: rooms(m, 2), FT_LIN | FT_BIASED, V_LIN_INST, "fastz", rooms=0),
     Entry("r_room_in_nested_list", lambda m: rooms(m, 5, nested=True), FT_LIN | FT_BIASED, V_LIN_INST, "fastz", rooms=1),
     Entry("r_two_rooms", lambda m: rooms(m, 5, two=True), FT_LIN | FT_BIASED, V_LIN_INST, "fastz", rooms=2),
+    # Operands outside the exact contract's short-core ranges in the path kernels (DESIGN.md "Numerics", the
+    # guard inventory): origins above and below 2^60 in one wave, MRT_F_SLOWDIV rect planes (planes off zero
+    # drop SIG_CORNELL), boxes of a bvh_node tree at 2^50, mesh normals normalize cannot take its short path
+    # on.  `without`: the unscaled / ordinary-plane graph.
+    Entry("s_scaled_2p54", lambda m: (lookalike(m, scale=2.0 ** 54, glass=True), lookalike(m, glass=True)), CORNELL, V_LIN_INST, "fastz",
+          rooms=0),  # (MRT_F_SLOWDIV walls are no room candidates)
+    Entry("s_scaled_2p53_open_room", lambda m: (lookalike(m, closed=False, scale=2.0 ** 53, glass=True), lookalike(m, closed=False, glass=True)),
+          CORNELL, V_LIN_INST, "fastz", rooms=0),
+    # (planes at 1e-30 render the ordinary-plane image bit for bit at the host leg's size, so that graph cannot
+    # be the `without`: the graph without its box is, as for b_cornell_lookalike)
+    Entry("s_slowdiv_planes", lambda m: (lookalike(m, planes=1e-30), lookalike(m, planes=1e-30, with_box=False)), CORNELL, V_LIN_INST,
+          "fastz", rooms=1),
+    Entry("s_slowdiv_planes_small", lambda m: (lookalike(m, scale=0.125, planes=2.0 ** -80), lookalike(m)), CORNELL, V_LIN_INST, "fastz",
+          rooms=1),
+    Entry("s_tree_scaled", b_tree_scaled, SKY_TREE, V_SKY, "fastz", hooks=(GEN, NOBVHW), rooms=0),
+    # fast_leg=False: the tolerance contract normalises by v_rsq_f32, which answers these normals (sums of 0,
+    # ~1e-30, ~1e25: |n|^2 is 0 or inf in float) differently from the reference's a / sqrt(|a|^2) -- a zero or
+    # NaN normal where the reference has inf or NaN -- and the paths part: measured at 128 x 128 x 64, rays
+    # 3023808 against 3881302 (-22%, bound 1%), mean diff -1.379e-01 (bound 2e-3), rmse 1.159e+01 (bound
+    # 0.05), image finite.  Outside the tolerance contract's operand range (DESIGN.md "Numerics contracts").
+    Entry("s_mesh_scaled_and_degenerate_normals", lambda m: (degenerate_normals(m), room_mesh_lookalike(m, False)),
+          ROOM_MESH | SIG_ROOM_MESH, V_ROOM_MESH, "fastz", hooks=(GEN, NOSIG), rooms=1, fast_leg=False),
 ]
 IDS = [e.name for e in CATALOGUE]
 

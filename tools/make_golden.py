@@ -8,6 +8,8 @@ Fixtures (all small; data only -- inputs and expected outputs):
   kat_pdf.npz             pdf_value / pdf_generate of spheres, rects and object_lists (`--only-pdf`)
   scene_<id>.json.gz      scene graph dump of select_scene (camera, primitives, BVH topology)
   hits_<id>.npy           closest-hit KATs: rays vs scene.objects->hit()
+  edge_hits_<id>.npz      the same for the edge-operand rays of tests/edge_rays.py (scenes 5-8, the 2048-ray
+                          selection, read by the harness from a file: `--only-edge`)
   stream_<id>.npz         stream-matched render: per-path radiance + ray counts + draw() image
   stream_5_mode1.npz      same for draw2() (mode 1) accumulation
   shipped_5.npz           as-shipped multithreaded reference render (statistical parity)
@@ -216,7 +218,35 @@ def refseq(tmp):
             print("refseq", sid, mode, meta)
 
 
+EDGE_SCENES = (5, 6, 7, 8)
+
+
+def edge_hits(tmp):
+    """edge_hits_<sid>.npz: the exact reference build's closest hits of the rays the host test casts
+    (tests/test_edge_rays_host.py batch()), in the hits_<sid>.npz layout."""
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+    import miniraytracer_amd as mrt
+    from test_edge_rays_host import batch
+    for sid in EDGE_SCENES:
+        w, h = SCENE_SIZES[sid]
+        _, rays, _ = batch(mrt, f"scene_{sid}")
+        rows = np.zeros((len(rays), 8), dtype=np.float32)
+        rows[:, 0:3], rows[:, 3:6], rows[:, 6] = rays["o"], rays["d"], rays["time"]
+        rows[:, 7] = rays["inside"].astype(np.int32).view(np.float32)
+        src, fn = os.path.join(tmp, "rays.f32"), os.path.join(tmp, "h.npy")
+        rows.tofile(src)
+        run(EXACT, ["--h-mode", "hits", "-width", w, "-height", h, "--h-rays", src, "--h-out", fn] + scene_args(sid))
+        rec = np.load(fn)
+        assert rec.shape == (len(rays), 16) and np.array_equal(rec[:, :8].view(np.uint32), rows.view(np.uint32))
+        np.savez_compressed(os.path.join(OUT, f"edge_hits_{sid}.npz"), rays=rec)
+        print("edge_hits", sid, len(rec), "rays,", int((rec[:, 8].view(np.int32) != 0).sum()), "hit")
+
+
 def main():
+    if "--only-edge" in sys.argv:
+        with tempfile.TemporaryDirectory() as tmp:
+            edge_hits(tmp)
+        return
     if "--only-refseq" in sys.argv:
         with tempfile.TemporaryDirectory() as tmp:
             refseq(tmp)
@@ -275,6 +305,7 @@ def main():
             fn = os.path.join(tmp, "h.npy")
             run(EXACT, ["--h-mode", "hits", "-width", w, "-height", h, "--h-n", 2048, "--h-out", fn] + scene_args(sid))
             np.savez_compressed(os.path.join(OUT, f"hits_{sid}.npz"), rays=np.load(fn))
+        edge_hits(tmp)
 
         # 4. stream-matched renders with per-path radiance / ray counts
         def stream(sid, w, h, spp, depth, mode, name):
