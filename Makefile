@@ -17,7 +17,7 @@ CSRC     = miniraytracer_amd/csrc
 OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
-           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_cast.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
+           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_cast.o $(OBJDIR)/mrt_probe.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
            $(OBJDIR)/mrt_temporal.o $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
@@ -74,6 +74,12 @@ $(OBJDIR)/mrt_aux.o: $(CSRC)/mrt_aux.hip $(HDRS)
 
 # the ray queries (mrt_cast_kernel<F>): the same, in a translation unit of its own
 $(OBJDIR)/mrt_cast.o: $(CSRC)/mrt_cast.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(HIPDEV) -DMRT_FAST=0 -c $< -o $@
+
+# the radiance queries (mrt_probe_kernel<F>) and mrt_radiance_fold, host and device from
+# include/mrt_radiance.h: the same, in a translation unit of its own
+$(OBJDIR)/mrt_probe.o: $(CSRC)/mrt_probe.hip include/mrt_radiance.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(HIPDEV) -DMRT_FAST=0 -c $< -o $@
 
@@ -147,7 +153,21 @@ build/claim_check: tools/claim_check.cpp $(HDRS)
 claim-check: build/claim_check
 	build/claim_check
 
+# The radiance queries' host side -- the CPU backend's trace loop and level rows, the probe helpers,
+# mrt_radiance_fold -- stand-alone under the same sanitizers (host code only, nothing preloaded; not
+# part of `all`): tools/probe_check.cpp.  Without UBSan's alignment check: mrt_cpu_scene_create copies the
+# view's triangle arrays as float4 from the blob's 8-byte-aligned storage, which that check stops at
+# before any of the code under test runs.
+PROBE_CHECK_SRC = tools/probe_check.cpp $(CSRC)/mrt_cpu.hip $(CSRC)/mrt_probe.hip $(CSRC)/mrt_tables.hip \
+                  $(CSRC)/scene_builder.cpp $(CSRC)/mrt_common.cpp
+build/probe_check: $(PROBE_CHECK_SRC) include/mrt_radiance.h include/mrt_adaptive.h $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) $(HOSTFMA) --offload-host-only -x hip -DMRT_FAST=0 -DMRT_PROBE_HOST_ONLY=1 $(SANFLAGS) -Xarch_host -fno-sanitize=alignment $(PROBE_CHECK_SRC) -ldl -o $@
+
+probe-check: build/probe_check
+	build/probe_check
+
 clean:
 	rm -rf build miniraytracer_amd/libmrt.so bin oracle/liboracle.so
 
-.PHONY: all clean tables-check temporal-check claim-check
+.PHONY: all clean tables-check temporal-check claim-check probe-check

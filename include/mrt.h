@@ -23,6 +23,8 @@
  *                                         sequence; main() renders one still frame
  *   mrt_cast_rays / mrt_cast_rays_device  scene.objects->hit(r, 0.001f, FLT_MAX, rec) for a caller's
  *                                         own rays                          scene_object.h:22, main.cpp:71
+ *   mrt_trace_rays / mrt_trace_rays_device trace(r, 0) for a caller's own rays  main.cpp:66-118
+ *   mrt_radiance_fold                     draw()'s per-pixel sum, NaN rule and clamp  main.cpp:150-175
  *
  * Threading: one host thread per device; calls on distinct scenes are thread-safe, calls on the
  * same scene handle are not reentrant.
@@ -418,6 +420,85 @@ mrt_status mrt_cast_rays_device(mrt_scene* s, const mrt_ray* d_rays, uint32_t n,
  *   time = cam->time0, tmax = +inf, inside = 0, reserved = 0
  * MRT_ERR_INVALID: null, x >= width, y >= height, a zero size. */
 mrt_status mrt_camera_pixel_ray(const mrt_camera* cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, mrt_ray* out);
+
+/* ---- radiance queries -----------------------------------------------------------------------------
+ * (an addition to this ABI; the reference's trace(r, 0), main.cpp:66, is what draw() calls per
+ * sample.)  Path-traced radiance along caller rays: light and irradiance probes, lightmap texels,
+ * radiance caches, cameras that are not the reference's (panorama, fisheye, orthographic, a measured
+ * lens), "how bright is it at the point I just picked".
+ *
+ * Record i of a batch (i = 0 .. n-1):
+ *   the ray     ray(o, d, time, inside) exactly as in the ray queries: d need not be of unit length,
+ *               make_ray normalises it and takes the direction mask from the argument; inside
+ *               non-zero counts as 1.
+ *   the stream  the path draws from the PCG32 whose two words are rng_state and rng_inc, used as
+ *               given: not re-seeded, and an even rng_inc is not an error.  mrt_probe_seed fills them
+ *               as pcg32_srandom(splitmix64(seed ^ path_id), path_id) leaves them: the render's keying.
+ *   the path    trace(r, 0) of main.cpp:66-118 under the exact numerics contract: segments until the
+ *               path ends, at most max_bounces + 1 of them, folded deepest-first as the recursion
+ *               returns.
+ *   the result  L = the folded radiance as trace() returns it -- the NaN rule and the luminance clamp
+ *               are draw()'s, not trace()'s, and are not applied (mrt_radiance_fold applies them);
+ *               rays = the path's trace() calls (its segments).
+ * No record is rejected: a non-finite o or d yields what the arithmetic yields, and the call never
+ * faults.  Both backends return the same bits, and a batch cut in two is the whole.
+ * n == 0: MRT_OK, nothing read, written or enqueued.  MRT_ERR_INVALID: a null pointer; a device
+ * pointer that is not 16-byte aligned; a device form on a CPU-backend scene. */
+typedef struct mrt_probe { float o[3], time; float d[3]; uint32_t inside; uint64_t rng_state, rng_inc; } mrt_probe;   /* 48 B */
+typedef struct mrt_radiance { float L[3]; uint32_t rays; } mrt_radiance;                                           /* 16 B */
+void mrt_probe_seed(uint64_t seed, uint64_t path_id, mrt_probe* p);
+/* Host records, both backends; returns when out[] is written.  rays_out (may be NULL): the sum of
+ * out[i].rays, added up on the host.  On a GPU scene it stages through device buffers, a level
+ * workspace and a stream of its own, in pieces of at most MRT_TRACE_PIECE records, and waits only for
+ * that work. */
+#define MRT_TRACE_PIECE (1u << 20)
+mrt_status mrt_trace_rays(mrt_scene* s, const mrt_probe* probes, uint32_t n, uint32_t max_bounces, mrt_radiance* out, uint64_t* rays_out);
+/* GPU backend only.  The bytes of fold-level storage mrt_trace_rays_device takes for the kernel's
+ * full grid and for one wave: lanes * max(max_bounces, 1) * 16, lanes = 64 for one wave.  Both depend
+ * only on the scene's device and max_bounces. */
+mrt_status mrt_trace_rays_workspace(const mrt_scene* s, uint32_t max_bounces, uint64_t* bytes_full, uint64_t* bytes_min);
+/* GPU backend only; device records, 16-byte aligned (d_work too).  Enqueued on `stream`: nothing is
+ * synchronised and nothing is allocated (capturable: a replay traces whatever d_probes then holds).
+ * It reads the scene tables and d_probes, writes d_out[0..n) and uses d_work[0..work_bytes) as
+ * scratch, nothing else -- nothing of the render workspace, so it needs no mrt_prepare and may sit
+ * between two mrt_render_device calls on one stream without changing either.  The grid comes from
+ * work_bytes: as many whole waves as the workspace has level rows for, capped at the full grid (and at
+ * the waves n records can occupy); fewer bytes than one wave needs is MRT_ERR_INVALID.  The result
+ * does not depend on the grid. */
+mrt_status mrt_trace_rays_device(mrt_scene* s, const mrt_probe* d_probes, uint32_t n, uint32_t max_bounces, mrt_radiance* d_out, void* d_work,
+                                 uint64_t work_bytes, void* stream);
+/* draw()'s pixel (main.cpp:150-175) over groups of consecutive records: out[g] (a float4, w = 0) is
+ * the mode-0 fold of records g*group .. g*group + group - 1 in record order -- a sample with a
+ * non-finite channel is replaced by the running sum (main.cpp:162-164) -- divided by `group` and
+ * clamped to max_luminance.  One definition for host and device (include/mrt_radiance.h): the same
+ * bits, and the bits of mrt_render's pixel when the records are the pixel's paths in sample order.
+ * MRT_ERR_INVALID: a null pointer, group == 0, a device pointer that is not 16-byte aligned;
+ * n_groups == 0 is MRT_OK.  The device form is enqueued on `stream` (no sync, no allocation). */
+mrt_status mrt_radiance_fold(const mrt_radiance* rad, uint32_t n_groups, uint32_t group, float max_luminance, float* rgb /* n_groups float4 */);
+mrt_status mrt_radiance_fold_device(const mrt_radiance* d_rad, uint32_t n_groups, uint32_t group, float max_luminance,
+                                    float* d_rgb /* n_groups float4 */, void* stream);
+/* Host only.  The start of the render's path (pixel, sample) under `cam` and d: the stream keyed by
+ * path_id = pixel * ns + sample under d->seed (ns = sqrt_samples^2), the sample-grid offsets of
+ * main.cpp:319-332 (sample = i * sqrt_samples + j: ((i + 0.5) / sq, (j + 0.5) / sq)), then
+ * camera::get_ray's arithmetic (camera.h:38-44): o, the UN-normalised direction argument, time,
+ * inside = 0, and the stream's two words as they stand AFTER the camera's draws.  mrt_trace_rays of
+ * it is the render's path: same radiance bits, same ray count.  Reads d->width, height,
+ * sqrt_samples and seed.  MRT_ERR_INVALID: null, a zero size, pixel >= width * height,
+ * sample >= ns. */
+mrt_status mrt_camera_path_probe(const mrt_camera* cam, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, mrt_probe* out);
+/* Host only.  The same grid and keying for an equirectangular camera at p->pos: 360 by 180 degrees,
+ * the image centre looks at p->lookat, p->up is up; no lens (aperture, vfov, aspect and focus_dist
+ * are not read).  With (u, v, w) the camera frame of p (camera.h:27-29: w = normalize(pos - lookat),
+ * u = normalize(cross(up, w)), v = cross(w, u)), (x, y) the pixel (row 0 = bottom) and (dx, dy) the
+ * sample's grid offsets, in float32 without contraction, in this order:
+ *   s = ((float)x + dx) / (float)width,  t = ((float)y + dy) / (float)height
+ *   phi = (s - 0.5f) * 6.2831855f,  theta = (t - 0.5f) * 3.1415927f
+ *   a = cos(theta) * sin(phi),  b = sin(theta),  c = cos(theta) * cos(phi)     (mrt_mathfn.h mrt_sinf / mrt_cosf)
+ *   d = ((a * u + b * v) - c * w),  o = pos
+ *   time = fma(time1 - time0, randf, time0) with the path's first draw (camera.h:41), inside = 0
+ * and the stream's words after that one draw.  MRT_ERR_INVALID: as mrt_camera_path_probe, or a
+ * degenerate frame (mrt_make_camera's rule for pos, lookat, up, time0, time1). */
+mrt_status mrt_pano_probe(const mrt_camera_params* p, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, mrt_probe* out);
 
 /* ---- multi-GPU: the framebuffer gather over RCCL (xGMI) ---------------------------------------
  * The reference's seam is main.cpp:347-382 (the worker threads over one work_queue) writing

@@ -63,6 +63,74 @@ def camera_pixel_rays(cam, width, height, xs, ys):
     return out
 
 
+# mrt_probe / mrt_radiance (include/mrt.h "radiance queries"), byte for byte
+PROBE_DTYPE = np.dtype([("o", "<f4", (3,)), ("time", "<f4"), ("d", "<f4", (3,)), ("inside", "<u4"), ("rng_state", "<u8"), ("rng_inc", "<u8")])
+RADIANCE_DTYPE = np.dtype([("L", "<f4", (3,)), ("rays", "<u4")])
+assert PROBE_DTYPE.itemsize == 48 and RADIANCE_DTYPE.itemsize == 16
+_U64 = 2 ** 64 - 1
+
+
+def probe_seed(seed, path_id):
+    """mrt_probe_seed (include/mrt.h): the (rng_state, rng_inc) words of the render's stream for path_id
+    under `seed`, as pcg32_srandom(splitmix64(seed ^ path_id), path_id) leaves them."""
+    p = np.zeros(1, dtype=PROBE_DTYPE)
+    lib().mrt_probe_seed(C.c_uint64(int(seed) & _U64), C.c_uint64(int(path_id) & _U64), C.c_void_p(p.ctypes.data))
+    return int(p["rng_state"][0]), int(p["rng_inc"][0])
+
+
+def _path_probes(fn, what, first, desc, pixels, samples):
+    px, sm = np.broadcast_arrays(np.asarray(pixels, dtype=np.int64), np.asarray(samples, dtype=np.int64))
+    px, sm = px.reshape(-1), sm.reshape(-1)
+    if ((px < 0) | (sm < 0) | (px >= 2 ** 32) | (sm >= 2 ** 32)).any():
+        raise ValueError(f"{what}: a pixel or sample outside uint32")
+    out = np.zeros(px.size, dtype=PROBE_DTYPE)
+    base = out.ctypes.data
+    for k in range(px.size):
+        check(fn(C.byref(first), C.byref(desc), int(px[k]), int(sm[k]), C.c_void_p(base + 48 * k)), what)
+    return out
+
+
+def camera_path_probes(cam, desc, pixels, samples):
+    """mrt_camera_path_probe (include/mrt.h) for each (pixels[k], samples[k]) (broadcast against each
+    other): the starts of the render's paths under the MrtCamera `cam` and `desc` -- origin,
+    un-normalised direction, time and the stream after the camera's draws -- as a PROBE_DTYPE array.
+    Renderer.trace_rays of them at desc's depth is the render's paths."""
+    return _path_probes(lib().mrt_camera_path_probe, "mrt_camera_path_probe", cam, desc, pixels, samples)
+
+
+def pano_probes(params, desc, pixels, samples):
+    """mrt_pano_probe (include/mrt.h): the same grid and keying for an equirectangular camera at
+    params.pos (an MrtCameraParams: 360 x 180 degrees, the image centre looks at lookat, up is up)."""
+    return _path_probes(lib().mrt_pano_probe, "mrt_pano_probe", params, desc, pixels, samples)
+
+
+def _as_radiance(rad, group):
+    a = np.asarray(rad)
+    if a.dtype != RADIANCE_DTYPE:
+        raise ValueError("radiance_fold: a RADIANCE_DTYPE array")
+    a = np.ascontiguousarray(a).reshape(-1)
+    if group < 1 or a.size % group:
+        raise ValueError("radiance_fold: the records must be whole groups")
+    return a
+
+
+def radiance_fold(rad, group, max_luminance=1000.0):
+    """mrt_radiance_fold (include/mrt.h) on the host: draw()'s pixel over each `group` consecutive
+    RADIANCE_DTYPE records -- the sum in record order with the NaN rule, divided by group, clamped to
+    max_luminance -- as a float32 (n / group, 4) array (w = 0)."""
+    a = _as_radiance(rad, group)
+    out = np.zeros((a.size // group, 4), dtype=np.float32)
+    check(lib().mrt_radiance_fold(C.c_void_p(a.ctypes.data), a.size // group, group, max_luminance, C.c_void_p(out.ctypes.data)), "mrt_radiance_fold")
+    return out
+
+
+def radiance_fold_device(d_rad_ptr, n_groups, group, d_rgb_ptr, max_luminance=1000.0, stream_ptr=0):
+    """The same on device records (torch data_ptr()s: n_groups * group mrt_radiance, n_groups float4,
+    16-byte aligned), enqueued on a HIP stream."""
+    check(lib().mrt_radiance_fold_device(C.c_void_p(d_rad_ptr or None), n_groups, group, max_luminance, C.c_void_p(d_rgb_ptr or None),
+                                         C.c_void_p(stream_ptr)), "mrt_radiance_fold_device")
+
+
 def default_params():
     p = MrtParams()
     lib().mrt_default_params(C.byref(p))
@@ -246,6 +314,34 @@ class Renderer:
         enqueued on a HIP stream: nothing synchronised, nothing allocated (capturable)."""
         check(lib().mrt_cast_rays_device(self._h, C.c_void_p(d_rays_ptr or None), n, C.c_uint64(int(seed) & (2 ** 64 - 1)),
                                          C.c_void_p(d_hits_ptr or None), C.c_void_p(stream_ptr)), "mrt_cast_rays_device")
+
+    def trace_rays(self, probes, depth=32):
+        """Path-traced radiance along caller rays (include/mrt.h mrt_trace_rays), both backends:
+        (records, rays) -- a RADIANCE_DTYPE array, one record per probe (L as trace() returns it, the
+        path's ray count), and the total of the ray counts.  probes: a PROBE_DTYPE array (e.g.
+        camera_path_probes, pano_probes, or your own rays with probe_seed streams)."""
+        p = np.asarray(probes)
+        if p.dtype != PROBE_DTYPE:
+            raise ValueError("probes: a PROBE_DTYPE array")
+        p = np.ascontiguousarray(p).reshape(-1)
+        out = np.zeros(p.size, dtype=RADIANCE_DTYPE)
+        rays = C.c_uint64()
+        check(lib().mrt_trace_rays(self._h, C.c_void_p(p.ctypes.data), p.size, depth, C.c_void_p(out.ctypes.data), C.byref(rays)), "mrt_trace_rays")
+        return out, rays.value
+
+    def trace_rays_workspace(self, depth=32):
+        """(bytes_full, bytes_min) of fold-level storage for trace_rays_device at `depth`: the kernel's
+        full grid and one wave (GPU)."""
+        full, least = C.c_uint64(), C.c_uint64()
+        check(lib().mrt_trace_rays_workspace(self._h, depth, C.byref(full), C.byref(least)), "mrt_trace_rays_workspace")
+        return full.value, least.value
+
+    def trace_rays_device(self, d_probes_ptr, n, d_out_ptr, d_work_ptr, work_bytes, depth=32, stream_ptr=0):
+        """The same on device records (torch data_ptr()s of n mrt_probe / n mrt_radiance and a workspace
+        of work_bytes, all 16-byte aligned), enqueued on a HIP stream: nothing synchronised, nothing
+        allocated (capturable).  The grid follows work_bytes (trace_rays_workspace)."""
+        check(lib().mrt_trace_rays_device(self._h, C.c_void_p(d_probes_ptr or None), n, depth, C.c_void_p(d_out_ptr or None),
+                                          C.c_void_p(d_work_ptr or None), work_bytes, C.c_void_p(stream_ptr)), "mrt_trace_rays_device")
 
     def render_adaptive(self, desc, params=None, cancel=None):
         """Adaptive render (include/mrt.h mrt_render_adaptive), both backends: desc as the base pass, then

@@ -229,6 +229,22 @@ def lib():
     L.mrt_cast_rays_device.restype = st
     L.mrt_camera_pixel_ray.argtypes = [C.POINTER(MrtCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     L.mrt_camera_pixel_ray.restype = st
+    L.mrt_probe_seed.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
+    L.mrt_probe_seed.restype = None
+    L.mrt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mrt_trace_rays.restype = st
+    L.mrt_trace_rays_workspace.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mrt_trace_rays_workspace.restype = st
+    L.mrt_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.mrt_trace_rays_device.restype = st
+    L.mrt_radiance_fold.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]
+    L.mrt_radiance_fold.restype = st
+    L.mrt_radiance_fold_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+    L.mrt_radiance_fold_device.restype = st
+    L.mrt_camera_path_probe.argtypes = [C.POINTER(MrtCamera), C.POINTER(MrtRenderDesc), C.c_uint32, C.c_uint32, C.c_void_p]
+    L.mrt_camera_path_probe.restype = st
+    L.mrt_pano_probe.argtypes = [C.POINTER(MrtCameraParams), C.POINTER(MrtRenderDesc), C.c_uint32, C.c_uint32, C.c_void_p]
+    L.mrt_pano_probe.restype = st
     _lib = L
     return L
 
@@ -254,4 +270,6 @@ EXPORTS = [
     "mrt_make_camera", "mrt_scene_camera_params", "mrt_scene_set_camera", "mrt_scene_set_camera_device",
     "mrt_default_temporal_params", "mrt_reproject", "mrt_reproject_device",
     "mrt_cast_rays", "mrt_cast_rays_device", "mrt_camera_pixel_ray",
+    "mrt_probe_seed", "mrt_trace_rays", "mrt_trace_rays_workspace", "mrt_trace_rays_device", "mrt_radiance_fold",
+    "mrt_radiance_fold_device", "mrt_camera_path_probe", "mrt_pano_probe",
 ]

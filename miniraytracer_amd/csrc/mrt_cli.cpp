@@ -36,6 +36,10 @@
 // other flags give and focuses the lens on what it hits: focus = t * -dot(d^, w) in float32, printed as
 // "focusat X Y: focus=..." (%.9g: -focus with that number renders the same image); a miss prints
 // "focusat X Y: miss" and leaves the focus alone.  With -frames it applies once, to frame 0's camera.
+// -pano renders a 360 x 180 degree equirectangular frame from the camera's position through the
+// radiance queries (mrt_pano_probe -> mrt_trace_rays -> mrt_radiance_fold; exact numerics, either
+// backend), written and tone-mapped as usual: the camera flags give position, look-at (the image
+// centre) and up; -aperture is ignored (no lens); -gpus above 1 is refused.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -186,6 +190,30 @@ static int run_sequence(const mrt_params& p, std::vector<mrt_scene*>& scenes, st
     return 0;
 }
 
+// -pano: the frame through the radiance queries instead of mrt_render -- every pixel's samples as
+// equirectangular probes at the camera's position (mrt_pano_probe, the render's grid and keying),
+// traced (mrt_trace_rays, exact contract, either backend) and folded per pixel (mrt_radiance_fold),
+// in pieces of whole pixels of at most about 2^16 records.
+static mrt_status render_pano(mrt_scene* scene, const mrt_camera_params& cp, const mrt_render_desc& d, std::vector<float>& img, uint64_t* rays) {
+    const uint64_t ns = (uint64_t)d.sqrt_samples * d.sqrt_samples, npx = (uint64_t)d.width * d.height;
+    if (ns > 0xFFFFFFFFull || npx > 0xFFFFFFFFull) return MRT_ERR_INVALID;
+    const uint64_t piece_px = std::max<uint64_t>(1, (1u << 16) / ns);
+    std::vector<mrt_probe> probes((size_t)(std::min(piece_px, npx) * ns));
+    std::vector<mrt_radiance> rad(probes.size());
+    *rays = 0;
+    for (uint64_t p0 = 0; p0 < npx; p0 += piece_px) {
+        const uint32_t m = (uint32_t)std::min(piece_px, npx - p0);
+        for (uint32_t k = 0; k < m; k++)
+            for (uint32_t s = 0; s < ns; s++)
+                if (mrt_status st = mrt_pano_probe(&cp, &d, (uint32_t)(p0 + k), s, &probes[(size_t)k * ns + s])) return st;
+        uint64_t r = 0;
+        if (mrt_status st = mrt_trace_rays(scene, probes.data(), (uint32_t)(m * ns), d.max_bounces, rad.data(), &r)) return st;
+        *rays += r;
+        if (mrt_status st = mrt_radiance_fold(rad.data(), m, (uint32_t)ns, d.max_luminance, img.data() + (size_t)p0 * 4)) return st;
+    }
+    return MRT_OK;
+}
+
 int main(int argc, char** argv) {
     mrt_params p;
     if (mrt_parse_argv(argc, argv, &p) != MRT_OK) return 0;  // -help
@@ -213,11 +241,12 @@ int main(int argc, char** argv) {
     const char *vfov = nullptr, *aperture = nullptr, *focus = nullptr, *frames_s = nullptr;
     int lookfrom_i = 0, lookat_i = 0;
     double orbit_deg = 0.0;
-    bool temporal = false, have_orbit = false;
+    bool temporal = false, have_orbit = false, pano = false;
     int pick_xy[2] = {-1, -1}, focusat_xy[2] = {-1, -1};
     for (int i = 1; i < argc; i++) {
         const bool v1 = i + 1 < argc, v3 = i + 3 < argc;
         if (!strcmp(argv[i], "-temporal")) temporal = true;
+        if (!strcmp(argv[i], "-pano")) pano = true;
         if (!strcmp(argv[i], "-lookfrom") && v3) lookfrom = argv[lookfrom_i = i + 1];
         if (!strcmp(argv[i], "-lookat") && v3) lookat = argv[lookat_i = i + 1];
         if (!strcmp(argv[i], "-vfov") && v1) vfov = argv[i + 1];
@@ -257,6 +286,19 @@ int main(int argc, char** argv) {
     }
     bool have_adaptive = false;
     for (int i = 1; i < argc; i++) have_adaptive |= !strcmp(argv[i], "-adaptive");
+    if (pano) {
+        if (p.gpus > 1) {
+            fprintf(stderr, "-pano: the radiance queries run on one scene context (-gpus 1)\n");
+            return 1;
+        }
+        if (have_adaptive || frames_s || aux || denoise >= 0 || (gather && !strcmp(gather, "rccl"))) {
+            fprintf(stderr, "-pano: renders one frame, without -adaptive, -frames, -aux, -denoise or -gather rccl\n");
+            return 1;
+        }
+        p.gpus = 1;
+        p.numerics = 0;  // mrt_trace_rays runs the exact contract
+        aperture = nullptr;  // no lens
+    }
     if (have_adaptive && (adaptive < 1 || adaptive > 4)) {
         fprintf(stderr, "-adaptive: 1 to 4 refinement passes\n");
         return 1;
@@ -404,7 +446,8 @@ int main(int argc, char** argv) {
 
     auto t0 = std::chrono::steady_clock::now();  // main.cpp:375
     std::vector<std::thread> th;
-    for (int r = 0; r < world; r++)
+    if (pano) sts[0] = render_pano(scenes[0], cp, descs[0], img, &rays[0]);
+    for (int r = 0; r < world && !pano; r++)
         th.emplace_back([&, r] {
             sts[r] = have_adaptive ? mrt_render_adaptive(scenes[r], &descs[r], &ap, img.data(), mom.data(), &rays[r], nullptr)
                      : use_rccl    ? mrt_render_gather(scenes[r], comms[r], &descs[r], r == 0 ? img.data() : nullptr, &rays[r])

@@ -14,6 +14,10 @@ mrt_status mrt_cpu_render(mrt_cpu_scene* c, const mrt_render_desc* d, float* rgb
 mrt_status mrt_cpu_render_aux(mrt_cpu_scene* c, const mrt_render_desc* d, float* normal_out, float* albedo_out);
 // ray queries (mrt_cast_rays; arguments checked by the caller): host records
 mrt_status mrt_cpu_cast_rays(mrt_cpu_scene* c, const mrt_ray* rays, uint32_t n, uint64_t seed, mrt_hit* hits);
+// radiance queries (mrt_trace_rays; arguments checked by the caller): host records.  The host-only
+// helpers of that section (mrt_probe_seed, mrt_camera_path_probe, mrt_pano_probe) are defined beside
+// it, where the camera's arithmetic is compiled for the host.
+mrt_status mrt_cpu_trace_rays(mrt_cpu_scene* c, const mrt_probe* probes, uint32_t n, uint32_t max_bounces, mrt_radiance* out);
 // the adaptive render (mrt_render_adaptive; arguments checked by the caller)
 mrt_status mrt_cpu_render_adaptive(mrt_cpu_scene* c, const mrt_render_desc* d, const mrt_adaptive_params* p, float* rgb_out, float* moments_out,
                                    uint64_t* rays_out, const volatile int* cancel);

@@ -35,6 +35,7 @@
 #include <chrono>
 #include <mutex>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -42,6 +43,7 @@
 #include "mrt_tables.h"
 #include "mrt_aux.h"
 #include "mrt_cast.h"
+#include "mrt_probe.h"
 #include "mrt_moments.h"
 #include "../../include/mrt_adaptive.h"
 
@@ -524,6 +526,113 @@ mrt_status mrt_cpu_cast_rays(mrt_cpu_scene* c, const mrt_ray* rays, uint32_t n, 
     for (uint32_t i = 1; i < nt; i++) pool.emplace_back(work);
     work();
     for (std::thread& t : pool) t.join();
+    return MRT_OK;
+}
+
+// Radiance queries (include/mrt.h mrt_trace_rays): probe_one (mrt_probe.h) over the batch -- per
+// record trace(r, 0) from the caller's ray and stream -- on worker threads that take 64 records at a
+// time, each with level rows of its own.
+template <uint32_t F>
+static void trace_some(const mrt_cpu_scene* c, const mrt_probe* probes, uint32_t n, uint32_t max_bounces, mrt_radiance* out,
+                       std::atomic<uint64_t>& next) {
+    const uint32_t rows = std::max<uint32_t>(max_bounces, 1);
+    Stacks st(c->T, rows);
+    const LStack Ls{st.frames.data(), st.rays.data(), st.mesh.data(), st.save.data(), 0u, nullptr, 0u};
+    const LevStore<0> lev{st.lev.data(), rows, 0u, 0u};
+    for (;;) {
+        const uint64_t k0 = next.fetch_add(64, std::memory_order_relaxed);
+        if (k0 >= n) break;
+        for (uint64_t k = k0; k < std::min<uint64_t>(k0 + 64, n); k++) {
+            ProbeRec q;
+            memcpy(&q, probes + k, sizeof q);
+            const ProbeOut o = probe_one<F>(c->S, q, max_bounces, lev, Ls);
+            memcpy(out + k, &o, sizeof o);
+        }
+    }
+}
+
+mrt_status mrt_cpu_trace_rays(mrt_cpu_scene* c, const mrt_probe* probes, uint32_t n, uint32_t max_bounces, mrt_radiance* out) {
+    uint32_t nt = std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    nt = (uint32_t)std::min<uint64_t>(nt, std::max<uint64_t>(((uint64_t)n + 255) / 256, 1));
+    std::atomic<uint64_t> next{0};
+    auto work = [&]() {
+        if (c->feats & FT_LIN) trace_some<F_LIN>(c, probes, n, max_bounces, out, next);
+        else trace_some<F_GEN>(c, probes, n, max_bounces, out, next);
+    };
+    std::vector<std::thread> pool;
+    for (uint32_t i = 1; i < nt; i++) pool.emplace_back(work);
+    work();
+    for (std::thread& t : pool) t.join();
+    return MRT_OK;
+}
+
+extern "C" void mrt_probe_seed(uint64_t seed, uint64_t path_id, mrt_probe* p) {
+    if (!p) return;
+    Pcg rng;
+    pcg_seed(rng, splitmix64(seed ^ path_id), path_id);
+    p->rng_state = rng.state;
+    p->rng_inc = rng.inc;
+}
+
+// (pixel, sample) of a desc -> the path's stream and its image coordinates, as render_tiles forms them:
+// the sample grid of main.cpp:319-332 in float, u and v by IEEE division
+static mrt_status probe_path_key(const char* who, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, Pcg& rng, float* u, float* v) {
+    if (d->width == 0 || d->height == 0 || d->sqrt_samples == 0) return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": a zero size").c_str());
+    const uint64_t sq = d->sqrt_samples, ns = sq * sq;
+    if ((uint64_t)pixel >= (uint64_t)d->width * d->height || sample >= ns)
+        return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": pixel or sample outside the render").c_str());
+    const uint32_t x = pixel % d->width, y = pixel / d->width;
+    const uint32_t i = (uint32_t)(sample / sq), j = (uint32_t)(sample % sq);
+    const float dx = ((float)i + 0.5f) / (float)d->sqrt_samples, dy = ((float)j + 0.5f) / (float)d->sqrt_samples;
+    *u = ((float)x + dx) / (float)d->width;
+    *v = ((float)y + dy) / (float)d->height;
+    const uint64_t path_id = (uint64_t)pixel * ns + sample;
+    pcg_seed(rng, splitmix64(d->seed ^ path_id), path_id);
+    return MRT_OK;
+}
+
+static void probe_put(mrt_probe* out, f3 o, f3 dir, float time, const Pcg& rng) {
+    memset(out, 0, sizeof *out);
+    out->o[0] = o.x, out->o[1] = o.y, out->o[2] = o.z;
+    out->d[0] = dir.x, out->d[1] = dir.y, out->d[2] = dir.z;
+    out->time = time;
+    out->rng_state = rng.state;
+    out->rng_inc = rng.inc;
+}
+
+extern "C" mrt_status mrt_camera_path_probe(const mrt_camera* cam, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, mrt_probe* out) {
+    if (!cam || !d || !out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_camera_path_probe: null");
+    Pcg rng;
+    float u, v;
+    if (mrt_status st = probe_path_key("mrt_camera_path_probe", d, pixel, sample, rng, &u, &v)) return st;
+    DScene S{};  // camera_ray_args reads the camera through S.camp, nothing else
+    S.camp = cam;
+    f3 o, dir;
+    float time;
+    camera_ray_args(S, rng, u, v, &o, &dir, &time);
+    probe_put(out, o, dir, time, rng);
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_pano_probe(const mrt_camera_params* p, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, mrt_probe* out) {
+    if (!p || !d || !out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_pano_probe: null");
+    // the frame (u, v, w) as the camera's constructor makes it; the lens parameters are not read
+    mrt_camera_params q = *p;
+    q.vfov_deg = 90.0f;
+    q.aspect = 1.0f;
+    q.aperture = 0.0f;
+    q.focus_dist = 1.0f;
+    mrt_camera cam;
+    if (mrt_status st = mrt_make_camera(&q, &cam)) return st;
+    Pcg rng;
+    float s, t;
+    if (mrt_status st = probe_path_key("mrt_pano_probe", d, pixel, sample, rng, &s, &t)) return st;
+    const float phi = (s - 0.5f) * 6.2831855f, theta = (t - 0.5f) * 3.1415927f;
+    const float ct = mrt_cosf(theta);
+    const float a = ct * mrt_sinf(phi), b = mrt_sinf(theta), c = ct * mrt_cosf(phi);
+    const f3 dir = sub(add(fmul(a, ld3(cam.u)), fmul(b, ld3(cam.v))), fmul(c, ld3(cam.w)));
+    const float time = ref_fma(p->time1 - p->time0, randf(rng), p->time0);  // camera.h:41
+    probe_put(out, ld3(cam.origin), dir, time, rng);
     return MRT_OK;
 }
 

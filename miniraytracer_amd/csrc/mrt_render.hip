@@ -27,6 +27,7 @@
 #include "mrt_launch.h"
 #include "mrt_aux.h"
 #include "mrt_cast.h"
+#include "mrt_probe.h"
 #include "mrt_tables.h"
 #include "mrt_cpu.h"
 #include "mrt_moments.h"
@@ -438,6 +439,13 @@ struct mrt_scene {
     hipStream_t cast_stream = nullptr;
     void* d_cast = nullptr;
     size_t d_cast_cap = 0;
+    // the same for the blocking mrt_trace_rays: staging records (probes, then radiance) and the
+    // fold-level workspace of its launches
+    hipStream_t trace_stream = nullptr;
+    void* d_trace = nullptr;
+    size_t d_trace_cap = 0;
+    void* d_trace_work = nullptr;
+    size_t d_trace_work_cap = 0;
 };
 
 // The LDS of a one-wave launch that only walks (the retrace and aux kernels): the generic machine's
@@ -663,6 +671,9 @@ extern "C" void mrt_scene_free(mrt_scene* s) {
     if (s->fstream) (void)hipStreamDestroy(s->fstream);
     if (s->cast_stream) (void)hipStreamDestroy(s->cast_stream);
     if (s->d_cast) (void)hipFree(s->d_cast);
+    if (s->trace_stream) (void)hipStreamDestroy(s->trace_stream);
+    if (s->d_trace) (void)hipFree(s->d_trace);
+    if (s->d_trace_work) (void)hipFree(s->d_trace_work);
     for (hipEvent_t e : {s->ev_kern, s->ev_fold[0], s->ev_fold[1]})
         if (e) (void)hipEventDestroy(e);
     delete s;  // (the workspace buffers release themselves: DevBuf)
@@ -1313,6 +1324,118 @@ extern "C" mrt_status mrt_cast_rays(mrt_scene* s, const mrt_ray* rays, uint32_t 
         if (mrt_status st = cast_launch(s, d_rays, m, seed + k0, d_hits, s->cast_stream)) return st;
         HIPCHK(hipMemcpyAsync(hits + k0, d_hits, (size_t)m * sizeof(mrt_hit), hipMemcpyDeviceToHost, s->cast_stream));
         HIPCHK(hipStreamSynchronize(s->cast_stream));
+    }
+    return MRT_OK;
+}
+
+// ---- radiance queries (include/mrt.h "radiance queries") ----
+// The probe kernel's full grid in waves: kProbeWavesPerCU per CU of the scene's device, whatever the
+// variant; a wave's level rows are 64 lanes x max(max_bounces, 1) float4.
+static uint64_t probe_full_waves(const mrt_scene* s) { return (uint64_t)s->n_cu * kProbeWavesPerCU; }
+static uint64_t probe_wave_bytes(uint32_t max_bounces) { return 64ull * std::max<uint32_t>(max_bounces, 1u) * 16ull; }
+
+// One mrt_probe_kernel launch over device records: the scene's variant from the probe table, one-wave
+// groups with the exact build's walk stacks (the cast launch's), `waves` of them, each lane striding
+// over the records.  It reads the scene tables and the probes and writes the records and the level
+// rows of its own lanes; nothing of the render workspace, so it needs no mrt_prepare, takes no part in
+// quiesce() and leaves no event behind.
+static mrt_status probe_launch(mrt_scene* s, const mrt_probe* d_probes, uint32_t n, uint32_t max_bounces, mrt_radiance* d_out, void* d_work,
+                               uint32_t waves, hipStream_t q) {
+    ProbeParams P{};
+    P.sc = s->S;
+    P.probes = (const ProbeRec*)d_probes;
+    P.out = (ProbeOut*)d_out;
+    P.lev = (float4*)d_work;
+    P.n = n;
+    P.max_bounces = max_bounces;
+    P.lev_rows = std::max<uint32_t>(max_bounces, 1u);
+    P.lds_frames = s->lds_frames;
+    P.lds_rays = s->lds_rays;
+    P.lds_mesh = s->lds_mesh;
+    P.lds_save = s->pl[0].lds_save;
+    const probe_kernel_t fn = probe_kernel_table().kernel[s->variant];
+    const size_t lds_bytes = walk_lds(s, P.lds_save).bytes();
+    hipLaunchKernelGGL(fn, dim3(waves), dim3(64), lds_bytes, q, P);
+    HIPCHK(hipGetLastError());
+    return MRT_OK;
+}
+
+// the waves a launch over n records runs with `work_bytes` of level rows (0: fewer than one wave's)
+static uint32_t probe_waves(const mrt_scene* s, uint32_t n, uint32_t max_bounces, uint64_t work_bytes) {
+    const uint64_t have = work_bytes / probe_wave_bytes(max_bounces);
+    return (uint32_t)std::min({have, probe_full_waves(s), ((uint64_t)n + 63u) / 64u});
+}
+
+extern "C" mrt_status mrt_trace_rays_workspace(const mrt_scene* s, uint32_t max_bounces, uint64_t* bytes_full, uint64_t* bytes_min) {
+    MRT_GPU_ONLY(s, "mrt_trace_rays_workspace");
+    if (!s || !bytes_full || !bytes_min) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_trace_rays_workspace: null");
+    *bytes_min = probe_wave_bytes(max_bounces);
+    *bytes_full = probe_full_waves(s) * probe_wave_bytes(max_bounces);
+    return MRT_OK;
+}
+
+extern "C" mrt_status mrt_trace_rays_device(mrt_scene* s, const mrt_probe* d_probes, uint32_t n, uint32_t max_bounces, mrt_radiance* d_out,
+                                            void* d_work, uint64_t work_bytes, void* stream) {
+    MRT_GPU_ONLY(s, "mrt_trace_rays_device");
+    if (!s) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_trace_rays_device: null");
+    if (n == 0) return MRT_OK;
+    if (!d_probes || !d_out || !d_work) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_trace_rays_device: null");
+    if (((uintptr_t)d_probes | (uintptr_t)d_out | (uintptr_t)d_work) & 15u)
+        return mrt_internal_fail(MRT_ERR_INVALID, "mrt_trace_rays_device: records or workspace not 16-byte aligned");
+    if (work_bytes < probe_wave_bytes(max_bounces))
+        return mrt_internal_fail(MRT_ERR_INVALID, "mrt_trace_rays_device: workspace below one wave's level rows (mrt_trace_rays_workspace)");
+    HIPCHK(hipSetDevice(s->device));
+    return probe_launch(s, d_probes, n, max_bounces, d_out, d_work, probe_waves(s, n, max_bounces, work_bytes), (hipStream_t)stream);
+}
+
+extern "C" mrt_status mrt_trace_rays(mrt_scene* s, const mrt_probe* probes, uint32_t n, uint32_t max_bounces, mrt_radiance* out,
+                                     uint64_t* rays_out) {
+    if (!s) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_trace_rays: null");
+    if (n == 0) {
+        if (rays_out) *rays_out = 0;
+        return MRT_OK;
+    }
+    if (!probes || !out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_trace_rays: null");
+    if (s->cpu) {
+        if (mrt_status st = mrt_cpu_trace_rays(s->cpu, probes, n, max_bounces, out)) return st;
+    } else {
+        HIPCHK(hipSetDevice(s->device));
+        // staged in pieces of at most MRT_TRACE_PIECE records (64 MiB of device records); the level rows
+        // of the waves a piece can occupy, at most the full grid's
+        uint32_t piece_max = MRT_TRACE_PIECE;
+        if (const char* e = getenv("MRT_TRACE_PIECE_RECORDS"))  // test hook: a small piece (tests/test_probe_gpu.py)
+            if (*e) piece_max = std::max(1u, std::min((uint32_t)strtoul(e, nullptr, 0), MRT_TRACE_PIECE));
+        const uint32_t piece = std::min(n, piece_max);
+        if (!s->trace_stream) HIPCHK(hipStreamCreateWithFlags(&s->trace_stream, hipStreamNonBlocking));
+        auto grow = [&](void** p, size_t* cap, size_t need, const char* what) {
+            if (*cap >= need) return MRT_OK;
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+            *cap = 0;
+            if (hipMalloc(p, need) != hipSuccess) return mrt_internal_fail(MRT_ERR_OOM, what);
+            *cap = need;
+            return MRT_OK;
+        };
+        if (mrt_status st = grow(&s->d_trace, &s->d_trace_cap, (size_t)piece * (sizeof(mrt_probe) + sizeof(mrt_radiance)), "mrt_trace_rays: device records"))
+            return st;
+        const uint64_t waves = std::min<uint64_t>(probe_full_waves(s), ((uint64_t)piece + 63u) / 64u);
+        const uint64_t work_bytes = waves * probe_wave_bytes(max_bounces);
+        if (mrt_status st = grow(&s->d_trace_work, &s->d_trace_work_cap, (size_t)work_bytes, "mrt_trace_rays: level workspace")) return st;
+        mrt_probe* const d_probes = (mrt_probe*)s->d_trace;
+        mrt_radiance* const d_out = (mrt_radiance*)((char*)s->d_trace + (size_t)piece * sizeof(mrt_probe));  // (48 * piece: 16-byte aligned)
+        for (uint64_t k0 = 0; k0 < n; k0 += piece) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(piece, n - k0);
+            HIPCHK(hipMemcpyAsync(d_probes, probes + k0, (size_t)m * sizeof(mrt_probe), hipMemcpyHostToDevice, s->trace_stream));
+            if (mrt_status st = probe_launch(s, d_probes, m, max_bounces, d_out, s->d_trace_work, probe_waves(s, m, max_bounces, work_bytes), s->trace_stream))
+                return st;
+            HIPCHK(hipMemcpyAsync(out + k0, d_out, (size_t)m * sizeof(mrt_radiance), hipMemcpyDeviceToHost, s->trace_stream));
+            HIPCHK(hipStreamSynchronize(s->trace_stream));
+        }
+    }
+    if (rays_out) {
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < n; i++) total += out[i].rays;
+        *rays_out = total;
     }
     return MRT_OK;
 }
