@@ -206,7 +206,10 @@ mrt_status mrt_kernel_ms(mrt_scene* s, float* path_ms, uint32_t* launches);
 
 /* Which path kernel the scene runs: feature bits of the scene (FT_* of mrt_trace.h; bit 11 =
  * linear hit program, bit 14 = a volume bounded by a sub-program, DESIGN.md "Kernels"), dynamic LDS bytes per workgroup, grid size in
- * workgroups, threads per workgroup, the BVH nodes each workgroup keeps in LDS, and the build of
+ * workgroups (of the last render's path-kernel launches; before any render, and for every blocking
+ * render, the resident grid, a multiple of n_cu; an MRT_RF_FOLD_ASYNC render of a kernel that leaves
+ * wave slots to its retrace and fold -- DESIGN.md round 14 -- runs that grid less a multiple of the
+ * launch's 8 work partitions, which need not be a multiple of n_cu), threads per workgroup, the BVH nodes each workgroup keeps in LDS, and the build of
  * the kernel for the last render's numerics: MRT_BUILD_* (the tolerance contract runs the fast,
  * the denormal-flushing or the path-exact build per kernel variant). */
 #define MRT_BUILD_EXACT 0u
@@ -219,7 +222,7 @@ typedef struct mrt_kernel_info {
        scene's upload (rounding-critical light samples); handover_lost: listed
        paths beyond a launch's list capacity (they keep their fast radiance; 0 in every BASELINE
        config).  Reading them waits for the scene's last render (its fold included).  n_cu: the compute
-       units of the scene's device, which the grid is a multiple of (0 on the CPU backend) */
+       units of the scene's device, which the resident grid is a multiple of (0 on the CPU backend) */
     uint32_t n_cu;
     uint64_t handed_over;
     uint64_t handover_lost;

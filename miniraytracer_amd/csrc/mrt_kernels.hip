@@ -956,11 +956,17 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
 // written over the fast one in the launch's radiance buffer, before the fold.  A few hundred to a
 // few thousand paths per launch: one-wave groups over the list, one path per lane; the last group
 // to finish clears the list for the next launch.  (The launch's ray count stays the fast paths'.)
+// The Cornell variant at eight waves per SIMD, that is at most 64 VGPRs (one spilled): under
+// MRT_RF_FOLD_ASYNC its waves run beside the next launch's path kernel, each in the slot a 64-VGPR
+// path wave left free (mrt_render.hip kSideSlots).  The other variants' launches keep their grids
+// and their retrace its registers.
 template <uint32_t F>
 static constexpr bool kRetrace = MRT_TABLE_PEX && MRT_FWD_FOLD && (F & FT_BIASED) != 0 && !kPathExact<F>;
+template <uint32_t F>
+static constexpr uint32_t kRetraceWpe = MRT_SIG_OF(F) == SIG_CORNELL ? 8u : 1u;
 #if MRT_TABLE_PEX
 template <uint32_t F>
-__global__ void __launch_bounds__(64) mrt_retrace_kernel(PathParams P) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRetraceWpe<F>))) mrt_retrace_kernel(PathParams P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t lane = threadIdx.x & 63u;
     const LStack Ls = lds_stacks(WaveLds{P.lds_frames, P.lds_rays, P.lds_mesh, P.lds_save}, lds, lane);

@@ -152,18 +152,24 @@ __global__ void __launch_bounds__(256) mrt_fold_kernel(const float* __restrict__
 // pixels grid-strided with FOLD_ASYNC_DEPTH samples in flight -- the same operations in the same
 // order as mrt_fold_kernel (bit-identical): from +0 or the accumulator, into the accumulator or,
 // for the render's last launch, finished into the output with the counters reset.
+// kSide: the launch left side slots free (kSideSlots) and the fold is that many one-wave groups, each
+// with two batches of FOLD_SIDE_DEPTH samples in flight.
 #ifndef MRT_FOLD_ASYNC_GROUPS
 #define MRT_FOLD_ASYNC_GROUPS 1  // 256-thread groups per CU: one wave per SIMD
 #endif
 #ifndef FOLD_ASYNC_DEPTH
 #define FOLD_ASYNC_DEPTH 8
 #endif
+#ifndef FOLD_SIDE_DEPTH
+#define FOLD_SIDE_DEPTH 6  // (two batches of 6 take 60 VGPRs; of 8 spill 19)
+#endif
 #ifndef MRT_FOLD_ASYNC_WG
 #define MRT_FOLD_ASYNC_WG 256  // threads per group
 #endif
 #ifndef MRT_FOLD_ASYNC_WPE
-#define MRT_FOLD_ASYNC_WPE 8  // (register cap 64: FOLD_ASYNC_DEPTH 8 takes 46)
+#define MRT_FOLD_ASYNC_WPE 8  // (register cap 64, a side slot's: FOLD_ASYNC_DEPTH 8 takes 46)
 #endif
+template <bool kSide>
 __global__ void __launch_bounds__(MRT_FOLD_ASYNC_WG) __attribute__((amdgpu_waves_per_eu(MRT_FOLD_ASYNC_WPE)))
 mrt_fold_async_kernel(const float* __restrict__ rad, float4* __restrict__ acc, uint32_t npix, uint32_t s0, uint32_t s1, uint32_t mode,
                       float max_lum, FoldEnd fe) {
@@ -180,15 +186,46 @@ mrt_fold_async_kernel(const float* __restrict__ rad, float4* __restrict__ acc, u
         const float* q = rad + (size_t)lp * 3;
         const size_t stride = (size_t)npix * 3;
         uint32_t s = s0;
-        for (; s + FOLD_ASYNC_DEPTH <= s1; s += FOLD_ASYNC_DEPTH) {
-            f3 v[FOLD_ASYNC_DEPTH];
+        if constexpr (kSide) {
+            // the loads of one batch are in flight while the other is folded: beside a path kernel the
+            // wave waits its turn for every instruction, so the adds take as long as the loads
+            auto load = [&](f3(&v)[FOLD_SIDE_DEPTH], uint32_t at) {
 #pragma unroll
-            for (int k = 0; k < FOLD_ASYNC_DEPTH; k++) {
-                const float* e = q + (size_t)(s - s0 + k) * stride;
-                v[k] = f3{__builtin_nontemporal_load(e), __builtin_nontemporal_load(e + 1), __builtin_nontemporal_load(e + 2)};
+                for (int k = 0; k < FOLD_SIDE_DEPTH; k++) {
+                    const float* e = q + (size_t)(at - s0 + k) * stride;
+                    v[k] = f3{__builtin_nontemporal_load(e), __builtin_nontemporal_load(e + 1), __builtin_nontemporal_load(e + 2)};
+                }
+            };
+            auto fold = [&](const f3(&v)[FOLD_SIDE_DEPTH]) {
+#pragma unroll
+                for (int k = 0; k < FOLD_SIDE_DEPTH; k++) c = fold_sample(c, v[k], s + k, mode, max_lum);
+                s += FOLD_SIDE_DEPTH;
+            };
+            if (s + FOLD_SIDE_DEPTH <= s1) {
+                f3 a[FOLD_SIDE_DEPTH], b[FOLD_SIDE_DEPTH];
+                load(a, s);
+                for (;;) {
+                    bool more = s + 2 * FOLD_SIDE_DEPTH <= s1;
+                    if (more) load(b, s + FOLD_SIDE_DEPTH);
+                    fold(a);
+                    if (!more) break;
+                    more = s + 2 * FOLD_SIDE_DEPTH <= s1;
+                    if (more) load(a, s + FOLD_SIDE_DEPTH);
+                    fold(b);
+                    if (!more) break;
+                }
             }
+        } else {
+            for (; s + FOLD_ASYNC_DEPTH <= s1; s += FOLD_ASYNC_DEPTH) {
+                f3 v[FOLD_ASYNC_DEPTH];
 #pragma unroll
-            for (int k = 0; k < FOLD_ASYNC_DEPTH; k++) c = fold_sample(c, v[k], s + k, mode, max_lum);
+                for (int k = 0; k < FOLD_ASYNC_DEPTH; k++) {
+                    const float* e = q + (size_t)(s - s0 + k) * stride;
+                    v[k] = f3{__builtin_nontemporal_load(e), __builtin_nontemporal_load(e + 1), __builtin_nontemporal_load(e + 2)};
+                }
+#pragma unroll
+                for (int k = 0; k < FOLD_ASYNC_DEPTH; k++) c = fold_sample(c, v[k], s + k, mode, max_lum);
+            }
         }
         for (; s < s1; s++) {
             const float* e = q + (size_t)(s - s0) * stride;
@@ -311,10 +348,28 @@ extern "C" mrt_status mrt_tonemap_device(const float* d_rgb, uint32_t n, const f
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
+// Wave slots an MRT_RF_FOLD_ASYNC launch leaves free for its own retrace and fold (DESIGN.md, round
+// 14): the Cornell walk kernel (box6_walk), whose one-wave groups take all eight wave slots of every
+// SIMD and which is bound by VALU issue, not by its wave count, is launched with kSideSlots fewer
+// groups (a multiple of MRT_NPART: every work partition gives up as many waves), and the retrace
+// and the fold, both one-wave groups of at most kSideVgprs registers, run in those slots on the
+// context's own stream while the next launch's path kernel already runs on the caller's.  Every
+// other kernel keeps its grid: the exact contract's Cornell kernel (seven waves per SIMD) lost 5 %
+// and the room + mesh kernel 1.5 % with the same slots gone (profiles/r14_ab.txt section 5).
+// 768 of the MI355X's 8192: the Cornell kernel is VALU-issue bound and runs no slower without them,
+// while the fold of a 3 GB launch in 512 slots outlasted the kernel beside it (profiles/r14_ab.txt).
+static constexpr int kSideSlots = 768;
+static constexpr int kSideVgprs = 64;
+// Beside the path kernel the fold lasts about as long as that kernel does (6.2 of 6.35 ms at depth 32),
+// and the launch after next waits for it: with a depth limit of 1 / 2 / 3 the kernel is short enough
+// for the step to become the fold's (+3.8 % / +1.0 % / -0.2 % against the full grid, -1.0 % from 4 on),
+// so launches of fewer than 4 bounces keep the full grid and the retrace on the render's stream.
+static constexpr uint32_t kSideMinBounces = 4;
 // one numerics build of the scene's path kernel (exact / fast): kernel, grid, registers
 struct PathLaunch {
     path_kernel_t fn = nullptr;
     int grid = 0;
+    int side = 0;  // one-wave groups an MRT_RF_FOLD_ASYNC launch leaves out of the grid: wave slots for its retrace and fold (kSideSlots)
     size_t lds_bytes = 0;
     uint32_t vgprs = 0;
     uint32_t wg = 64;     // threads per workgroup
@@ -323,6 +378,7 @@ struct PathLaunch {
     bool rewrite = false;   // the kernel runs the tolerance-contract program rewrite (s->prog_fast)
     path_kernel_t retrace = nullptr;  // the exact arithmetic for its rounding-critical paths (mrt_retrace_kernel)
     bool handover = false;  // the kernel hands its rounding-critical paths to it (fast arithmetic)
+    bool retrace_side = false;  // the retrace kernel fits a side slot (at most kSideVgprs registers)
     uint32_t walk_min = 32;  // resumable mesh walk threshold of this build (PathParams::walk_min)
 };
 
@@ -425,6 +481,7 @@ struct mrt_scene {
     uint32_t n_launch = 0;
     uint64_t last_paths = 0;
     uint32_t last_numerics = 0;
+    uint32_t last_grid = 0;  // path-kernel groups of the last render's launches (0: none yet)
     uint32_t prog_ops = 0;  // linear hit program length (0: generic machine)
     // the adaptive render's moments sink (internal, mrt_render_adaptive): while mom is set, every
     // launch chunk's radiance is also added to mom[mom_slots ? mom_slots[lp] : lp] (mrt_moments_kernel)
@@ -644,6 +701,16 @@ extern "C" mrt_status mrt_scene_upload(int device, const mrt_scene_view* v, mrt_
         // handed out, and visits at most MRT_STEAL_TRIES partitions (mrt_kernels.hip)
         if (L.grid < (int)MRT_NPART) return mrt_internal_fail(MRT_ERR_HIP, "path kernel grid smaller than the work partitions");
         s->max_threads = std::max(s->max_threads, (size_t)L.grid * L.wg);
+        // the slots of an async launch's side kernels (kSideSlots): the Cornell walk kernel at eight
+        // one-wave groups per SIMD, the register-bound grid
+        const int wps = std::min(8, 512 / vg);
+        if (tabs[k]->box6_walk[s->variant] && L.wg == 64u && nb == wps * 4 && wps == 8)
+            L.side = std::min(kSideSlots, L.grid / 2) / (int)MRT_NPART * (int)MRT_NPART;
+        if (L.side && L.retrace) {  // a retrace that does not fit a freed slot stays on the render's stream
+            hipFuncAttributes ra{};
+            HIPCHK(hipFuncGetAttributes(&ra, reinterpret_cast<const void*>(L.retrace)));
+            L.retrace_side = ra.numRegs <= kSideVgprs;
+        }
     }
     *out = owner.release();
     return MRT_OK;
@@ -728,7 +795,9 @@ static constexpr uint32_t kRetraceGroups = 256;
 // (Round 6: the retrace of an MRT_RF_FOLD_ASYNC launch beside the next launch's path kernel -- on the
 // context's fold stream, and there in one-wave slots the next kernel left free -- measured slower:
 // the previous launch's fold uses the GPU during the retrace's gap on the render's stream, and behind
-// the retrace on the fold stream it got only the free slots, profiles/r06_ab.txt sections 2 and 7.)
+// the retrace on the fold stream it got only the free slots, profiles/r06_ab.txt sections 2 and 7.
+// Round 14 does it with slots for both, a fold of one-wave groups and a retrace of at most 64
+// registers: kSideSlots.)
 
 #define MRT_GPU_ONLY(s, what) \
     if ((s) && (s)->cpu) return mrt_internal_fail(MRT_ERR_INVALID, what " is a GPU-backend entry point (scene on MRT_DEVICE_CPU)")
@@ -947,7 +1016,13 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
     // the rounding-critical paths' hand-over: tolerance contract, not the per-path debug output
     // (whose radiance is the fast kernel's own)
     const bool handover = PL.handover && !(d->flags & MRT_RF_PATH_DEBUG);
-    const int grid = PL.grid;
+    // MRT_RF_FOLD_ASYNC on a kernel that fills every SIMD: PL.side groups fewer, whose wave slots the
+    // launch's retrace and fold take on fstream (kSideSlots).  Per-path streams: which wave runs a
+    // path changes neither the image nor the ray total.
+    // (not below kSideMinBounces: a shallow launch's kernel is shorter than its fold runs beside it)
+    const int side = async && d->max_bounces >= kSideMinBounces ? PL.side : 0;
+    const int grid = PL.grid - side;
+    s->last_grid = (uint32_t)grid;
     for (uint32_t s0 = 0; s0 < ns; s0 += s->chunk) {
         uint32_t s1 = std::min(ns, s0 + s->chunk);
         const uint32_t par = async ? s->lpar : 0u;
@@ -997,11 +1072,19 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
         // this launch's rounding-critical paths, exact, into the radiance buffer before its fold (the
         // exact arithmetic walks the program as compiled: the tolerance contract's rewrite has ops -- a
         // room's slab test, one-step box instances -- only the fast builds compile)
+        // (with side slots: on fstream in front of the fold, so the caller's stream goes straight on to
+        // the next launch; the list it empties is its parity's, which the launch after next fills only
+        // after ev_fold[par])
+        const bool rside = side && PL.retrace_side;
+        if (rside) {
+            HIPCHK(hipEventRecord(s->ev_kern, q));
+            HIPCHK(hipStreamWaitEvent(s->fstream, s->ev_kern, 0));
+        }
         if (handover) {
             PathParams PR = P;
             PR.sc.prog = s->S.prog;
             PR.lds_save = s->lds_save;  // (the exact arithmetic parks a ray where the Cornell walk does not)
-            hipLaunchKernelGGL(PL.retrace, dim3(kRetraceGroups), dim3(64), walk_lds(s, PR.lds_save).bytes(), q, PR);
+            hipLaunchKernelGGL(PL.retrace, dim3(kRetraceGroups), dim3(64), walk_lds(s, PR.lds_save).bytes(), rside ? s->fstream : q, PR);
             HIPCHK(hipGetLastError());
         }
         // the last chunk's full fold finishes the render (no preview: no snapshot of acc needed;
@@ -1012,10 +1095,18 @@ extern "C" mrt_status mrt_render_device(mrt_scene* s, const mrt_render_desc* d, 
         const FoldEnd fe{last ? (float4*)d_local : nullptr, ns, last ? d_cnt : nullptr, last ? h_prog : nullptr,
                          last ? launches * MRT_CNT_SLOTS : 0u, last ? launches * MRT_NPART : 0u};
         if (async) {  // the fold on the fold stream, beside the next launch's path kernel
-            HIPCHK(hipEventRecord(s->ev_kern, q));
-            HIPCHK(hipStreamWaitEvent(s->fstream, s->ev_kern, 0));
-            hipLaunchKernelGGL(mrt_fold_async_kernel, dim3(s->n_cu * MRT_FOLD_ASYNC_GROUPS), dim3(MRT_FOLD_ASYNC_WG), 0, s->fstream, d_rad, s->d_acc.p, s->npix,
-                               s0, s1, d->mode, d->max_luminance, fe);
+            // (with side slots: one-wave groups, as many as the launch left free -- a 256-thread group
+            // needs a free slot on all four SIMDs of a CU at once)
+            if (!rside) {
+                HIPCHK(hipEventRecord(s->ev_kern, q));
+                HIPCHK(hipStreamWaitEvent(s->fstream, s->ev_kern, 0));
+            }
+            if (side)
+                hipLaunchKernelGGL(mrt_fold_async_kernel<true>, dim3(side), dim3(64), 0, s->fstream, d_rad, s->d_acc.p, s->npix, s0, s1, d->mode,
+                                   d->max_luminance, fe);
+            else
+                hipLaunchKernelGGL(mrt_fold_async_kernel<false>, dim3(s->n_cu * MRT_FOLD_ASYNC_GROUPS), dim3(MRT_FOLD_ASYNC_WG), 0, s->fstream, d_rad,
+                                   s->d_acc.p, s->npix, s0, s1, d->mode, d->max_luminance, fe);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(s->ev_fold[par], s->fstream));
             s->fold_pending[par] = true;
@@ -1582,7 +1673,7 @@ extern "C" mrt_status mrt_scene_kernel_info(const mrt_scene* s, mrt_kernel_info*
     out->kernel_features = kVariants[s->variant];
     const PathLaunch& L = s->pl[s->last_numerics];
     out->lds_bytes = (uint32_t)L.lds_bytes;
-    out->grid = (uint32_t)L.grid;
+    out->grid = s->last_grid ? s->last_grid : (uint32_t)L.grid;  // (an async launch with side slots: fewer groups)
     out->prog_ops = s->prog_ops;
     out->vgprs = L.vgprs;
     out->wg = L.wg;
