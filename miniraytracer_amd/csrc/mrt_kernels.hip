@@ -622,6 +622,16 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
                     ((MRT_LDS_AS v4f*)(uintptr_t)Ls.axes)[e] = v4f{v.x, v.y, v.z, 0.0f};
                 }
             }
+            // the light's quad in the sphere's slot of the axes (after the stores above, the sphere's
+            // unused axis among them: one wave's LDS stores land in order): the rect's extents and area
+            // from the launch's words, once per wave (mrt_sig.h cornell_light_quad), and whether a scatter's
+            // pdf can be negative (kCwPdfSigned): not under the walk's light with its area's sign clear --
+            // +0, positive, or a NaN of that sign
+            const LightQuad lq = cornell_light_quad(__uint_as_float(cw.light.b0), __uint_as_float(cw.light.b1),
+                                                    __uint_as_float(cw.light.b2), __uint_as_float(cw.light.b3));
+            if (lane == kLightQuadSlot * 3u) ((MRT_LDS_AS v4f*)(uintptr_t)Ls.axes)[kLightQuadSlot] = v4f{lq.ex, lq.ez, lq.area, 0.0f};
+            const bool area_ok = (__float_as_uint(lq.area) >> 31) == 0u;
+            cw.flags |= uniform_u32(S.biased != MRT_NONE && !(S.light_once && area_ok) ? 1u << kCwPdfSigned : 0u);
         }
         for (;;) {
             if constexpr (kBox6Walk<F>) cornell_words_hold(cw);
@@ -770,12 +780,19 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
             if constexpr (kBox6Walk<F>) { ps.r.o = pr.o; ps.r.inside = pr.inside; }
             if (want_ray) {
                 BSTATC(12, pr.kind != 0);
+                // Cornell walk: the light's area for the scatter's pdf below, the third word of the wave's
+                // light quad (mrt_sig.h cornell_light_quad) at a wave-uniform address, issued ahead of the
+                // ray's constructor, which covers its latency (one VGPR until finish_scatter).  A volatile
+                // read: a plain one is sunk into the pdf's block, where the code waits for it at once.
+                float light_area = 0.0f;
+                if constexpr (kBox6Walk<F> != 0u && (F & FT_BIASED) != 0u)
+                    light_area = *(const volatile MRT_LDS_AS float*)(uintptr_t)(Ls.axes + kLightQuadSlot * (kHitAxisWords * 4u) + 8u);
                 ps.r = make_ray(kBox6Walk<F> ? ps.r.o : pr.o, pr.dir, pr.time, kBox6Walk<F> ? ps.r.inside : pr.inside);
                 // the Cornell fast walk's light test, once per ray: the scatter's light pdf below and
                 // the next iteration's walk both read it (one VGPR across the back edge)
                 if constexpr (kBox6Walk<F>) ps.lt = cornell_light_t<F>(cw.light, ps.r);
                 PH_MARK(ph, 8);
-                if (pr.kind) finish_scatter<F, LK>(S, ps, lev, pr, cornell_ptr(cw));
+                if (pr.kind) finish_scatter<F, LK>(S, ps, lev, pr, cornell_ptr(cw), light_area);
             }
             PH_MARK(ph, 7);
         }

@@ -121,6 +121,8 @@ struct WaveLds {
     constexpr uint32_t queue_at() const { return box6 ? hit_words() : mesh_at() + queue_past_mesh(); }
     constexpr uint32_t claim_row_at() const { return queue_at() + kQueueRows * kLanes; }
     constexpr uint32_t axes_at() const { return claim_row_at() + kHitAxisWord0; }
+    // the light's quad (mrt_sig.h cornell_light_quad): the axes' slot of the sphere, whose axis is made per lane
+    constexpr uint32_t light_quad_at() const { return claim_row_at() + kLightQuadWord0; }
     constexpr uint32_t stride() const {
         return (frames * kFrameWords + rays * kRayWords + mesh + save + lev_k * kLevWords + pq) * kLanes + hit_words();
     }
@@ -138,6 +140,11 @@ static_assert(WaveLds{0, 0, 0, 0, 0, 13, true}.hit_table() * 4u == 0u, "the Corn
 static_assert(WaveLds{0, 0, 0, 0, 0, 13, true}.queue_at() * 4u == 672u, "the queue follows the hit table");
 static_assert(WaveLds{0, 0, 0, 0, 0, 13, true}.claim_row_at() == WaveLds{0, 0, 0, 0, 0, 13, true}.queue_at() + 12u * 64u, "claim row");
 static_assert(WaveLds{0, 0, 0, 0, 0, 13, true}.bytes() == 13u * 64u * 4u + 672u, "queue + hit table");
+static_assert(WaveLds{0, 0, 0, 0, 0, 13, true}.light_quad_at() == WaveLds{0, 0, 0, 0, 0, 13, true}.axes_at() + kHitSphere * kHitAxisWords &&
+                  WaveLds{0, 0, 0, 0, 0, 13, true}.light_quad_at() % 4u == 0u &&
+                  WaveLds{0, 0, 0, 0, 0, 13, true}.light_quad_at() + 4u <= WaveLds{0, 0, 0, 0, 0, 13, true}.stride(),
+              "the light's quad: the last quad of the claim row, 16-byte aligned, no LDS beyond what the wave had");
+static_assert(32u * WaveLds{0, 0, 0, 0, 0, 13, true}.bytes() <= 160u * 1024u, "eight waves per SIMD: 32 slices fit a CU's LDS");
 static_assert(WaveLds{1, 2, 3, 9, 0, 13, true}.frames_at() == 168u + 13u * 64u, "a Cornell walk kernel's stacks follow its queue");
 // the generic machine's 16-wave group: 3 frames, 2 rays, 24 mesh words, 2 fold levels, a 100-node treelet
 static_assert(WaveLds{3, 2, 24, 0, 2, 0, false, 16, 100}.bytes() == (size_t)16 * 64 * 4 * (3 * 2 + 2 * 11 + 24 + 0 + 2 * 4 + 0) + 100 * 64,

@@ -122,6 +122,18 @@ MRT_DFN float xz_pdf_of_hit(const float* f, f3 dir, bool h, float t) {
     const float pdf = dist_sq / (cosine * area);
     return h ? pdf : 0.0f;
 }
+// the same from the rect's area (f[1] - f[0]) * (f[3] - f[2]) made ahead, a rounded f32 of its own
+// there as here, and its side ns = f[5].  The cosine |dot(dir, (0, ns, 0))| as |dir.y * ns|: the dot
+// product adds dir.x * 0 and dir.z * 0 to dir.y * ns, signed zeros for a finite direction -- a sum
+// then differs from dir.y * ns (one rounding either way, contracted or not) in a zero's sign at most,
+// which the magnitude drops -- and a normalised direction's components are all finite or all NaN
+// (goes through the cases), so both forms are NaN together.
+MRT_DFN float xz_pdf_of_hit_area(float area, float ns, f3 dir, bool h, float t) {
+    const float dist_sq = t * t;
+    const float cosine = fabsf(dir.y * ns);
+    const float pdf = dist_sq / (cosine * area);
+    return h ? pdf : 0.0f;
+}
 template <uint32_t F>
 MRT_DFN float leaf_pdf_value(const DScene& S, const mrt_node& n, f3 origin, f3 dir, float time) {
     uint32_t k = MRT_NODE_KIND(n);
@@ -218,22 +230,25 @@ MRT_DFN f3 leaf_pdf_generate(const DScene& S, const mrt_node& n, f3 origin, floa
     return f3{1, 0, 0};
 }
 template <uint32_t F>
-MRT_DFN f3 biased_pdf_generate(const DScene& S0, f3 origin, float time, Pcg& rng, Draws& dr, const CornellWords* cw = nullptr) {
+MRT_DFN f3 biased_pdf_generate(const DScene& S0, f3 origin, float time, Pcg& rng, Draws& dr, const CornellWords* cw = nullptr,
+                               const v4f* lq = nullptr) {
     if constexpr (kBox6Walk<F>) {
         // the one biased leaf is op 3's rect bit for bit (DScene::light_once): xz_rect::pdf_generate
         // from the program's words, which the launch holds in scalar registers (mrt_sig.h CornellWords)
-        // -- the leaf's kind word and then, after a wait, its bounds were two dependent round trips
+        // -- the leaf's kind word and then, after a wait, its bounds were two dependent round trips --
+        // and from its extents as the wave made them once (*lq: the light's quad, mrt_sig.h
+        // cornell_light_quad, read by the caller ahead of the draws)
         if (light_once<F>(S0, cw)) {
             if (cornell_flag(cw, kCwBlist)) (void)dr.next(rng);  // object_list::pdf_generate's index draw (scene_object.h:72-77)
             const CornellRect& d = cw->light;
-            mrt_node n;
-            n.kind = MRT_K_XZ;
-            n.f[0] = __uint_as_float(d.b0);
-            n.f[1] = __uint_as_float(d.b1);
-            n.f[2] = __uint_as_float(d.b2);
-            n.f[3] = __uint_as_float(d.b3);
-            n.f[4] = __uint_as_float(d.k);
-            return leaf_pdf_generate<F>(S0, n, origin, time, rng, dr);
+            // leaf_pdf_generate's xz_rect, the extents n.f[1] - n.f[0] and n.f[3] - n.f[2] from the quad
+            // (each a rounded f32 of its own there as here: the explicit fma's operand)
+            float a = dr.next(rng);
+            float x = ref_fma(a, lq->x, __uint_as_float(d.b0));  // rect.cpp:105 (left to right)
+            float b = dr.next(rng);
+            float z = ref_fma(b, lq->y, __uint_as_float(d.b2));
+            dr.edge = fmaxf(fabsf(a - 0.5f), fabsf(b - 0.5f)) >= 0.5f - MRT_EDGE_TOL;
+            return sub(f3{x, __uint_as_float(d.k), z}, origin);
         }
     }
     const DScene& S = cold_scene<F>(S0);  // (the list's fields, read where they are used)
@@ -406,6 +421,32 @@ MRT_DFN void push_level(PathState& ps, const LevStore<LK>& lev, float4 lv) {
 #else
     lev.put(ps.nlev & ~LEV_LOUD, lv);
     ps.nlev = (ps.nlev + 1) | (quiet_level(lv) ? 0u : LEV_LOUD);
+#endif
+}
+
+// The same for a diffuse scatter's level in a Cornell walk kernel, whose launch has decided whether
+// its pdf can be negative at all (`pdf_signed`, wave-uniform: mrt_sig.h kCwPdfSigned).  Where it cannot
+// -- lv.w is +-0, positive or NaN -- the forward fold is the diffuse side alone: no compare, no second
+// exec region.  Either way the three products T * lv are made once, ahead of the branch (taken there
+// through an empty asm: left to the compiler, two of them were issued again on the diffuse side), and
+// every lane's operations and their values are push_level's.
+template <uint32_t LK>
+MRT_DFN void push_level_pdf(PathState& ps, const LevStore<LK>& lev, float4 lv, bool pdf_signed) {
+#if MRT_FWD_FOLD
+    (void)lev;
+    f3 p{ps.T.x * lv.x, ps.T.y * lv.y, ps.T.z * lv.z};
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(p.x), "+v"(p.y), "+v"(p.z));
+#endif
+    if (!pdf_signed) {
+        ps.T = f3{p.x / lv.w, p.y / lv.w, p.z / lv.w};
+        return;
+    }
+    if (lv.w < 0.0f) ps.T = p;
+    else ps.T = f3{p.x / lv.w, p.y / lv.w, p.z / lv.w};
+#else
+    (void)pdf_signed;
+    push_level(ps, lev, lv);
 #endif
 }
 
@@ -739,8 +780,14 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     // ds_read_b96 ran into LDS bank conflicts, measured), its unused fourth register kept allocated up
     // to the use below: reused at once, its write-after-write hazard made the code wait for the read
     // right here.
+    // A lane on the light side does not use the axis: it reads the light's quad (ex, ez, area, 0:
+    // mrt_sig.h cornell_light_quad) IN ITS PLACE -- the quad sits in the sphere's slot of the axes, so it
+    // is the same ds_read_b128 with the index selected (one v_cndmask of an inline constant), the same
+    // four registers -- and xz_rect::pdf_generate takes its extents from there instead of making
+    // b1 - b0 and b3 - b2 from the scalar words (a v_mov and a v_sub each).  The quad is the launch's
+    // light whatever the biased list holds: a scene whose pdf takes the leaf path reads it too and uses
+    // none of it.  Light-side lanes and sphere lanes read one address: a broadcast.
     v4f axq{0.0f, 0.0f, 0.0f, 0.0f};
-    if constexpr (kBox6Walk<F>) axq = *(const MRT_LDS_AS v4f*)(uintptr_t)(Ls.axes + hid * (kHitAxisWords * 4u));
     bool light;
     if constexpr (kBox6Walk<F>) {
         light = false;
@@ -748,6 +795,7 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
             light = pd.v < 0.5f;
             ps.rng.state = pd.state;
         }
+        axq = *(const MRT_LDS_AS v4f*)(uintptr_t)(Ls.axes + (light ? kLightQuadSlot : hid) * (kHitAxisWords * 4u));
     } else {
         light = ((F & FT_BIASED) && S.biased != MRT_NONE) && randf(ps.rng) < 0.5f;
     }
@@ -759,7 +807,10 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
     }
     BSTATC(7, light);
     if (light) {
-        pr->dir = biased_pdf_generate<F>(S, rec.p, r.time, ps.rng, dr, cw);
+        pr->dir = biased_pdf_generate<F>(S, rec.p, r.time, ps.rng, dr, cw, &axq);
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (kBox6Walk<F>) asm volatile("" ::"v"(axq.z), "v"(axq.w));  // (the quad's unused registers, as below)
+#endif
     } else if constexpr (kBox6Walk<F>) {
         if (lamb) {
             const f3 vec = random_cosine_direction_pre(dr.v0, dr.v1);
@@ -782,7 +833,8 @@ MRT_DFN bool trace_split(const DScene& S, PathState& ps, uint32_t max_bounces, c
 
 // the rest of a diffuse scatter once ps.r = make_ray(pr): mix_pdf value (main.cpp:84-102), level
 template <uint32_t F, uint32_t LK>
-MRT_DFN void finish_scatter(const DScene& S, PathState& ps, const LevStore<LK>& lev, const PendRay& pr, const CornellWords* cw = nullptr) {
+MRT_DFN void finish_scatter(const DScene& S, PathState& ps, const LevStore<LK>& lev, const PendRay& pr, const CornellWords* cw = nullptr,
+                            float light_area = 0.0f) {
     const Ray& sc = ps.r;
     float sval, spdf;
     if (pr.kind == 1u) {
@@ -801,18 +853,23 @@ MRT_DFN void finish_scatter(const DScene& S, PathState& ps, const LevStore<LK>& 
         float bv;
         if (light_once<F>(S, cw)) {
             // the biased list is the walk's light: xz_rect::pdf_value from the ray's one light test
-            // (ps.lt; the rect's words from op 3, the biased leaf's bit for bit)
+            // (ps.lt; the rect's words from op 3, the biased leaf's bit for bit; light_area: its area as the
+            // wave made it once, the third word of the light's quad, read by the caller ahead of the ray)
             const CornellRect& d = cw->light;
-            const float f[6] = {__uint_as_float(d.b0), __uint_as_float(d.b1), __uint_as_float(d.b2), __uint_as_float(d.b3),
-                                __uint_as_float(d.k), __uint_as_float(d.ns)};
-            bv = xz_pdf_of_hit(f, sc.d, !(ps.lt < 0.0f), ps.lt);
+            bv = xz_pdf_of_hit_area(light_area, __uint_as_float(d.ns), sc.d, !(ps.lt < 0.0f), ps.lt);
         } else {
             bv = biased_pdf_value<F>(cold_scene<F>(S), sc.o, sc.d, sc.time);
         }
         pdf_v = 0.5f * (bv + sval);
     }
     const float4 lv = make_float4(pr.att.x * spdf, pr.att.y * spdf, pr.att.z * spdf, pdf_v);
-    push_level(ps, lev, lv);
+    if constexpr (kBox6Walk<F>) {
+        // pdf_v = 0.5 (bv + sval) with sval the cosine pdf or 0 and bv = t^2 / (|cosine| area) or 0:
+        // with the area's sign clear, +0, positive or NaN (-0 would take the same side: -0 < 0 is false)
+        push_level_pdf(ps, lev, lv, cornell_flag(cw, kCwPdfSigned));
+    } else {
+        push_level(ps, lev, lv);
+    }
 }
 
 // the recursion's return path, deepest level first; the lane's levels are contiguous, so they

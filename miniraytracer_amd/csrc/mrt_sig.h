@@ -471,6 +471,30 @@ static_assert(sizeof(LinOp) == kHitWords * 4 && kHitLdsBytes % 16 == 0, "hit tab
 // mix of identities reads without a conflict -- and no LDS beyond what the wave had.
 static constexpr uint32_t kHitAxisWord0 = 8, kHitAxisWords = 4;
 static_assert(kHitAxisWord0 % 4 == 0 && kHitAxisWord0 + kHitCount * kHitAxisWords <= 64, "the axes fit the claim row, 16-byte aligned");
+// The light's quad (ex, ez, area, 0): the extents b1 - b0, b3 - b2 of op 3's rect and their product,
+// constants of the launch that xz_rect::pdf_generate and pdf_value (mrt_shade.h leaf_pdf_generate,
+// xz_pdf_of_hit) made from the scene words on the vector unit in every iteration -- a v_mov and a v_sub
+// per extent on each side, and the product: gfx950 takes one SGPR operand per instruction.  One lane
+// computes it once per wave, with those functions' expressions (cornell_light_quad), into the wave's
+// LDS, and both sides read it at a wave-uniform address (a broadcast: no bank conflict).  Its place is
+// the SPHERE's quad of the basis axes: the sphere's entry has no table normal, its axis is made per lane,
+// and its quad was in bounds and unused -- so the wave's LDS does not grow, and a lane on the light
+// side reads "the axis of identity kHitSphere" with the read the cosine side makes (mrt_shade.h
+// trace_split: a select of the index, an inline constant).  Three more SGPRs held for the launch
+// instead spilled; so does the address of a place of its own.
+static constexpr uint32_t kLightQuadSlot = kHitSphere;
+static constexpr uint32_t kLightQuadWord0 = kHitAxisWord0 + kLightQuadSlot * kHitAxisWords;  // in the claim row
+static_assert(kLightQuadWord0 % 4 == 0 && kLightQuadWord0 + 4 <= 64, "the light's quad: 16-byte aligned, inside the claim row");
+struct LightQuad {
+    float ex, ez, area;
+};
+// each a separately rounded f32, from b0..b3 in xz_pdf_of_hit's operand order; nothing is contracted
+// into a difference or into a product of two differences, under either contract's flags
+// (host and device alike: the table builder's test hook evaluates it on a view's words)
+__host__ __device__ __forceinline__ LightQuad cornell_light_quad(float b0, float b1, float b2, float b3) {
+    const float ex = b1 - b0, ez = b3 - b2;
+    return LightQuad{ex, ez, ex * ez};
+}
 struct CornellRec {
     float closest;
     uint32_t id;    // cornell_fast_hit: the hit's identity (kHitNone: none)
@@ -623,7 +647,13 @@ MRT_DFN const CornellWords* cornell_ptr(const NoCornellWords&) { return nullptr;
 // CornellWords::flags: the scene has a biased list; DScene::light_once; DScene::blist; per-path ray
 // counts are wanted (PathParams::path_rays).  Tested with a scalar bit compare where used
 // (cornell_words_hold keeps the test from being hoisted out of the path loop into a lane mask).
-enum : uint32_t { kCwBiased = 0, kCwLightOnce = 1, kCwBlist = 2, kCwPathRays = 3 };
+// kCwPdfSigned: a diffuse scatter's pdf may come out negative, which the fold reads as metal's "no pdf"
+// marker (mrt_shade.h push_level): decided once per launch.  Clear without a biased list (the cosine
+// pdf alone) and where the biased list is the walk's light and its area's sign is clear
+// (cornell_light_quad's: the upload does not refuse a rect with swapped bounds) -- the pdf is then a
+// sum of non-negative terms or NaN, and finish_scatter folds it without the marker's side
+// (push_level_pdf).  Set for any other biased list, whose leaves' areas nobody has looked at.
+enum : uint32_t { kCwBiased = 0, kCwLightOnce = 1, kCwBlist = 2, kCwPathRays = 3, kCwPdfSigned = 4 };
 MRT_DFN bool cornell_flag(const CornellWords* cw, uint32_t bit) { return ((cw->flags >> bit) & 1u) != 0u; }
 MRT_DFN void cornell_take1(CornellRect& d) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -751,7 +781,16 @@ MRT_DFN bool cornell_fast_hit(const CornellWords& cw, const Ray& r, float tmin, 
     if (w.id == kHitNone) return false;
     *hid = w.id;
     // the hit's entry of the wave's table: three 16-byte LDS reads at one per-lane address
+    // (the identity is < 16: a 24-bit multiply, one full-rate instruction, written out -- the compiler's
+    // own choice for the product and sum, __umul24 included, is a v_mov and a 64-bit multiply-add)
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(kHitLdsWords * 4u == 48u, "the multiplier below is an inline constant");
+    uint32_t eo;
+    asm("v_mul_u32_u24_e32 %0, 48, %1" : "=v"(eo) : "v"(w.id));
+    const uint32_t at = hits + eo;
+#else
     const uint32_t at = hits + w.id * (kHitLdsWords * 4u);
+#endif
     const MRT_LDS_AS v4f* e = (const MRT_LDS_AS v4f*)(uintptr_t)at;
     const v4f q0 = e[0], q1 = e[1], q2 = e[2];
     const float k = q0.w;

@@ -728,6 +728,22 @@ extern "C" int mrt_debug_cornell_hits(const mrt_scene_view* v, uint32_t* words, 
     return 0;
 }
 
+// Test hook (tests/test_cornell_light_gpu.py): the light's quad of a Cornell-shape view -- the extents and
+// area a Cornell walk kernel's waves compute once per launch from op 3's words (mrt_sig.h
+// cornell_light_quad, the same function, here in the host's arithmetic: no contraction), and op 3's four
+// bounds as the program holds them.  Returns 1 where the view is refused, 2 where it has another shape.
+extern "C" int mrt_debug_cornell_light_quad(const mrt_scene_view* v, float quad[4], float bounds[4]) {
+    SceneTables T;
+    if (mrt_internal_scene_tables(v, &T) != MRT_OK) return 1;
+    if (MRT_SIG_OF(T.features) != SIG_CORNELL) return 2;
+    const LinOp& l = T.prog[3];
+    const LightQuad q = cornell_light_quad(l.f[0], l.f[1], l.f[2], l.f[3]);
+    const float w[4] = {q.ex, q.ez, q.area, 0.0f};
+    memcpy(quad, w, sizeof w);
+    memcpy(bounds, l.f, 4 * sizeof(float));
+    return 0;
+}
+
 // Test hook (tests/test_tables_digest.py, tools/tables_digest.py): the tables as 17 words -- FNV-1a 64
 // over the length and bytes of nodes, wide, bwide, bprims, dmats, bleaf, prog, prog_fast (their
 // records have no padding), then blist, nbleaf, blazy, light_once, prog_ops, features, max_frames,
