@@ -17,7 +17,7 @@ CSRC     = miniraytracer_amd/csrc
 OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
-           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_cast.o $(OBJDIR)/mrt_probe.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
+           $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_cast.o $(OBJDIR)/mrt_probe.o $(OBJDIR)/mrt_probegen.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
            $(OBJDIR)/mrt_temporal.o $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
@@ -82,6 +82,13 @@ $(OBJDIR)/mrt_cast.o: $(CSRC)/mrt_cast.hip $(HDRS)
 $(OBJDIR)/mrt_probe.o: $(CSRC)/mrt_probe.hip include/mrt_radiance.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(HIPDEV) -DMRT_FAST=0 -c $< -o $@
+
+# the probe generators (mrt_gen_*_kernel) and their host forms from mrt_probegen.h: the exact contract
+# on both sides (no contraction; the host's explicit fma() as one instruction, as in the CPU backend),
+# in a translation unit of its own
+$(OBJDIR)/mrt_probegen.o: $(CSRC)/mrt_probegen.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -DMRT_FAST=0 $(if $(HOSTFMA),-Xarch_host $(HOSTFMA)) -c $< -o $@
 
 # the a-trous filter, host and device from include/mrt_denoise.h: no contraction on either side
 # (HIPFLAGS), the host's explicit fma() as one instruction (as in the CPU backend)
@@ -167,7 +174,19 @@ build/probe_check: $(PROBE_CHECK_SRC) include/mrt_radiance.h include/mrt_adaptiv
 probe-check: build/probe_check
 	build/probe_check
 
+# The probe generators' host forms stand-alone under the same sanitizers (host code only, nothing
+# preloaded; not part of `all`): tools/probegen_check.cpp runs the range forms at ragged ranges against
+# the per-record functions, and the surface probes on hand-made hits (misses, non-finite normals)
+PROBEGEN_CHECK_SRC = tools/probegen_check.cpp $(CSRC)/mrt_probegen.hip $(CSRC)/mrt_cpu.hip $(CSRC)/mrt_probe.hip $(CSRC)/mrt_tables.hip \
+                     $(CSRC)/scene_builder.cpp $(CSRC)/mrt_common.cpp
+build/probegen_check: $(PROBEGEN_CHECK_SRC) include/mrt_radiance.h include/mrt_adaptive.h $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) $(HOSTFMA) --offload-host-only -x hip -DMRT_FAST=0 -DMRT_PROBE_HOST_ONLY=1 -DMRT_PROBEGEN_HOST_ONLY=1 $(SANFLAGS) -Xarch_host -fno-sanitize=alignment $(PROBEGEN_CHECK_SRC) -ldl -o $@
+
+probegen-check: build/probegen_check
+	build/probegen_check
+
 clean:
 	rm -rf build miniraytracer_amd/libmrt.so bin oracle/liboracle.so
 
-.PHONY: all clean tables-check temporal-check claim-check probe-check
+.PHONY: all clean tables-check temporal-check claim-check probe-check probegen-check

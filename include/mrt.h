@@ -25,6 +25,9 @@
  *                                         own rays                          scene_object.h:22, main.cpp:71
  *   mrt_trace_rays / mrt_trace_rays_device trace(r, 0) for a caller's own rays  main.cpp:66-118
  *   mrt_radiance_fold                     draw()'s per-pixel sum, NaN rule and clamp  main.cpp:150-175
+ *   mrt_camera_path_probes / mrt_pano_probes / mrt_camera_pixel_rays / mrt_surface_probes (+ _device)
+ *                                         (new) whole ranges of ray and probe records made where they are
+ *                                         traced; the camera ranges are camera::get_ray  camera.h:38-44
  *
  * Threading: one host thread per device; calls on distinct scenes are thread-safe, calls on the
  * same scene handle are not reentrant.
@@ -423,6 +426,17 @@ mrt_status mrt_cast_rays_device(mrt_scene* s, const mrt_ray* d_rays, uint32_t n,
  *   time = cam->time0, tmax = +inf, inside = 0, reserved = 0
  * MRT_ERR_INVALID: null, x >= width, y >= height, a zero size. */
 mrt_status mrt_camera_pixel_ray(const mrt_camera* cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, mrt_ray* out);
+/* A range of them: record j (j = 0 .. n-1) is mrt_camera_pixel_ray(cam, width, height, pixel % width,
+ * pixel / width) bit for bit, pixel = first + j, row-major with row 0 at the bottom;
+ * first + n <= width * height.  The host form writes out[0..n).  The device form is enqueued on
+ * `stream`: nothing is synchronised and nothing is allocated (capturable); *cam is read at the call
+ * and travels in the kernel arguments, so a replay uses the captured camera; it writes d_out[0..n)
+ * (16-byte aligned) and nothing else, and takes no scene.
+ * n == 0: MRT_OK, nothing read, written or enqueued (null pointers are fine then).  MRT_ERR_INVALID:
+ * a null pointer, a misaligned d_out, a zero size, a range that ends past the image. */
+mrt_status mrt_camera_pixel_rays(const mrt_camera* cam, uint32_t width, uint32_t height, uint64_t first, uint32_t n, mrt_ray* out);
+mrt_status mrt_camera_pixel_rays_device(const mrt_camera* cam, uint32_t width, uint32_t height, uint64_t first, uint32_t n, mrt_ray* d_out,
+                                        void* stream);
 
 /* ---- radiance queries -----------------------------------------------------------------------------
  * (an addition to this ABI; the reference's trace(r, 0), main.cpp:66, is what draw() calls per
@@ -480,7 +494,14 @@ mrt_status mrt_trace_rays_device(mrt_scene* s, const mrt_probe* d_probes, uint32
 mrt_status mrt_radiance_fold(const mrt_radiance* rad, uint32_t n_groups, uint32_t group, float max_luminance, float* rgb /* n_groups float4 */);
 mrt_status mrt_radiance_fold_device(const mrt_radiance* d_rad, uint32_t n_groups, uint32_t group, float max_luminance,
                                     float* d_rgb /* n_groups float4 */, void* stream);
-/* Host only.  The start of the render's path (pixel, sample) under `cam` and d: the stream keyed by
+/* The ray total of device records in stream order: *d_rays += the sum of d_rad[i].rays, i = 0 .. n-1 (a
+ * device uint64 the caller zeroes, as mrt_render_device's d_rays) -- what mrt_trace_rays' rays_out is
+ * for host records, so a device chain copies back pixels and one total, not the records.  Enqueued on
+ * `stream`, no sync, no allocation (capturable).  n == 0: MRT_OK, nothing enqueued.  MRT_ERR_INVALID: a
+ * null pointer, d_rad not 16-byte aligned, d_rays not 8-byte aligned. */
+mrt_status mrt_radiance_rays_device(const mrt_radiance* d_rad, uint32_t n, uint64_t* d_rays, void* stream);
+/* One record on the host (ranges, on the host or the device: mrt_camera_path_probes below).  The start
+ * of the render's path (pixel, sample) under `cam` and d: the stream keyed by
  * path_id = pixel * ns + sample under d->seed (ns = sqrt_samples^2), the sample-grid offsets of
  * main.cpp:319-332 (sample = i * sqrt_samples + j: ((i + 0.5) / sq, (j + 0.5) / sq)), then
  * camera::get_ray's arithmetic (camera.h:38-44): o, the UN-normalised direction argument, time,
@@ -489,7 +510,8 @@ mrt_status mrt_radiance_fold_device(const mrt_radiance* d_rad, uint32_t n_groups
  * sqrt_samples and seed.  MRT_ERR_INVALID: null, a zero size, pixel >= width * height,
  * sample >= ns. */
 mrt_status mrt_camera_path_probe(const mrt_camera* cam, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, mrt_probe* out);
-/* Host only.  The same grid and keying for an equirectangular camera at p->pos: 360 by 180 degrees,
+/* One record on the host (ranges: mrt_pano_probes below).  The same grid and keying for an
+ * equirectangular camera at p->pos: 360 by 180 degrees,
  * the image centre looks at p->lookat, p->up is up; no lens (aperture, vfov, aspect and focus_dist
  * are not read).  With (u, v, w) the camera frame of p (camera.h:27-29: w = normalize(pos - lookat),
  * u = normalize(cross(up, w)), v = cross(w, u)), (x, y) the pixel (row 0 = bottom) and (dx, dy) the
@@ -502,6 +524,62 @@ mrt_status mrt_camera_path_probe(const mrt_camera* cam, const mrt_render_desc* d
  * and the stream's words after that one draw.  MRT_ERR_INVALID: as mrt_camera_path_probe, or a
  * degenerate frame (mrt_make_camera's rule for pos, lookat, up, time0, time1). */
 mrt_status mrt_pano_probe(const mrt_camera_params* p, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, mrt_probe* out);
+
+/* ---- probe generators -----------------------------------------------------------------------------
+ * Whole ranges of the records above, made on the host or -- the _device forms -- where they are traced:
+ * generate -> mrt_trace_rays_device -> mrt_radiance_fold_device is a chain of enqueues on one stream,
+ * and so is mrt_camera_pixel_rays_device -> mrt_cast_rays_device -> mrt_surface_probes_device -> trace
+ * -> fold.  Host and device forms return the same bits (one definition, csrc/mrt_probegen.h).
+ *
+ * Every device form: enqueued on `stream`; nothing is synchronised and nothing is allocated
+ * (capturable); cam, p and d are host structs, read at the call, that travel in the kernel arguments --
+ * a replay uses the captured values; it writes d_out[0..n) and nothing else; d_out and the other
+ * device pointers are 16-byte aligned.  No form takes a scene.
+ * Both forms: n == 0 (n_hits == 0) is MRT_OK -- nothing is read, written or enqueued, null pointers are
+ * fine then.  MRT_ERR_INVALID: a null pointer, a misaligned device pointer, a zero size, a range that
+ * ends past the render, and the per-record forms' own rules (a degenerate panorama frame, an image
+ * above 2^32 pixels: pixel indices are 32-bit).
+ *
+ * The two probe ranges.  Record j (j = 0 .. n-1) is path q = first + j of the render d, counted
+ * pixel-major: pixel = q / ns, sample = q % ns, ns = sqrt_samples^2, pixels row-major with row 0 at the
+ * bottom; first + n <= width * height * ns.  Record j of mrt_camera_path_probes equals
+ * mrt_camera_path_probe(cam, d, pixel, sample) bit for bit, record j of mrt_pano_probes equals
+ * mrt_pano_probe(p, d, pixel, sample).  A range of whole pixels in this order is what
+ * mrt_radiance_fold takes with group = ns. */
+mrt_status mrt_camera_path_probes(const mrt_camera* cam, const mrt_render_desc* d, uint64_t first, uint32_t n, mrt_probe* out);
+mrt_status mrt_camera_path_probes_device(const mrt_camera* cam, const mrt_render_desc* d, uint64_t first, uint32_t n, mrt_probe* d_out,
+                                         void* stream);
+mrt_status mrt_pano_probes(const mrt_camera_params* p, const mrt_render_desc* d, uint64_t first, uint32_t n, mrt_probe* out);
+mrt_status mrt_pano_probes_device(const mrt_camera_params* p, const mrt_render_desc* d, uint64_t first, uint32_t n, mrt_probe* d_out,
+                                  void* stream);
+/* Surface probes: cosine-distributed directions leaving the points of hit records (mrt_cast_rays'
+ * output) -- irradiance probes, lightmap texels, ambient occlusion with a sky.  With
+ * sq = sqrt_per_hit >= 1, P = sq^2 and n_hits * P < 2^32, record j = i * P + k belongs to hit i and
+ * stratum k of a sq x sq grid, in float32 without contraction, in this order:
+ *   a = k / sq,  b = k % sq
+ *   the stream  mrt_probe_seed(seed, first_id + j) (uint64 wrap), then u1 = randf, then u2 = randf; the
+ *               record holds the two words as they stand after the two draws.  A miss takes the draws
+ *               as well: the stream never depends on the hit, and a batch cut at c is two calls with
+ *               first_id and first_id + c * P.
+ *   r1 = ((float)a + u1) / (float)sq,  r2 = ((float)b + u2) / (float)sq            (IEEE division)
+ *   z = sqrt(1 - r2),  s = sqrt(r2)   (correctly rounded),   phi = (2 * 3.1415927f) * r1
+ *   vec = (cos(phi) * s, sin(phi) * s, z)                    (the sincos of mrt_mathfn.h mrt_sincos_d)
+ *   w = hits[i].n; with `rays` given, w = -n when dot(n, rays[i].d) > 0 (the normal faces the ray; a
+ *       NaN dot does not turn it)
+ *   d = onb(w) * vec  (onb.h:19-27),  o = hits[i].p,  time = rays ? rays[i].time : 0,  inside = 0
+ * The direction is cosine-weighted about w, so pi * mean(L) over a hit's P records estimates the
+ * irradiance there.  This is deliberately NOT the reference's random_cosine_direction, whose x and y
+ * carry a factor 2 (pcg.cpp:92-93) that the ray constructor then normalises into a distribution that
+ * is not cosine-weighted.  The reference's fixed tmin = 0.001 keeps the path off its own surface, as in
+ * every scatter.
+ * A miss (hits[i].mat == MRT_NO_HIT) gives o = d = 0, time = 0, inside = 0 and the stream's words;
+ * tracing that record returns what the arithmetic yields for a null direction (one segment, no fault).
+ * Callers mask by mat.  `rays` may be NULL; d_hits, d_rays and d_out are 16-byte aligned.
+ * MRT_ERR_INVALID also for sqrt_per_hit == 0 and n_hits * P >= 2^32. */
+mrt_status mrt_surface_probes(const mrt_hit* hits, const mrt_ray* rays /* may be NULL */, uint32_t n_hits, uint32_t sqrt_per_hit, uint64_t seed,
+                              uint64_t first_id, mrt_probe* out);
+mrt_status mrt_surface_probes_device(const mrt_hit* d_hits, const mrt_ray* d_rays /* may be NULL */, uint32_t n_hits, uint32_t sqrt_per_hit,
+                                     uint64_t seed, uint64_t first_id, mrt_probe* d_out, void* stream);
 
 /* ---- multi-GPU: the framebuffer gather over RCCL (xGMI) ---------------------------------------
  * The reference's seam is main.cpp:347-382 (the worker threads over one work_queue) writing

@@ -63,6 +63,30 @@ def camera_pixel_rays(cam, width, height, xs, ys):
     return out
 
 
+def _range_args(what, first, n):
+    first, n = int(first), int(n)
+    if first < 0 or first > _U64 or n < 0 or n >= 2 ** 32:
+        raise ValueError(f"{what}: first outside uint64 or n outside uint32")
+    return first, n
+
+
+def camera_pixel_ray_range(cam, width, height, first, n):
+    """mrt_camera_pixel_rays (include/mrt.h): the pinhole rays through the centres of pixels
+    first .. first + n - 1 (row-major, row 0 = bottom) in one call, a RAY_DTYPE array; record j equals
+    camera_pixel_rays' ray of pixel first + j."""
+    first, n = _range_args("camera_pixel_ray_range", first, n)
+    out = np.zeros(n, dtype=RAY_DTYPE)
+    check(lib().mrt_camera_pixel_rays(C.byref(cam), width, height, first, n, C.c_void_p(out.ctypes.data)), "mrt_camera_pixel_rays")
+    return out
+
+
+def camera_pixel_rays_device(cam, width, height, first, n, d_out_ptr, stream_ptr=0):
+    """The same into device records (a torch data_ptr() of n mrt_ray, 16-byte aligned), enqueued on a
+    HIP stream: nothing synchronised, nothing allocated (capturable; the camera is captured by value)."""
+    check(lib().mrt_camera_pixel_rays_device(C.byref(cam), width, height, int(first), int(n), C.c_void_p(d_out_ptr or None), C.c_void_p(stream_ptr)),
+          "mrt_camera_pixel_rays_device")
+
+
 # mrt_probe / mrt_radiance (include/mrt.h "radiance queries"), byte for byte
 PROBE_DTYPE = np.dtype([("o", "<f4", (3,)), ("time", "<f4"), ("d", "<f4", (3,)), ("inside", "<u4"), ("rng_state", "<u8"), ("rng_inc", "<u8")])
 RADIANCE_DTYPE = np.dtype([("L", "<f4", (3,)), ("rays", "<u4")])
@@ -104,6 +128,72 @@ def pano_probes(params, desc, pixels, samples):
     return _path_probes(lib().mrt_pano_probe, "mrt_pano_probe", params, desc, pixels, samples)
 
 
+def camera_path_probe_range(cam, desc, first, n):
+    """mrt_camera_path_probes (include/mrt.h): the starts of paths first .. first + n - 1 of the render
+    `desc` under the MrtCamera `cam`, counted pixel-major (pixel = q // ns, sample = q % ns), in one
+    call: a PROBE_DTYPE array whose record j equals camera_path_probes' record of that (pixel, sample)."""
+    first, n = _range_args("camera_path_probe_range", first, n)
+    out = np.zeros(n, dtype=PROBE_DTYPE)
+    check(lib().mrt_camera_path_probes(C.byref(cam), C.byref(desc), first, n, C.c_void_p(out.ctypes.data)), "mrt_camera_path_probes")
+    return out
+
+
+def camera_path_probes_device(cam, desc, first, n, d_out_ptr, stream_ptr=0):
+    """The same into device records (a torch data_ptr() of n mrt_probe, 16-byte aligned), enqueued on a
+    HIP stream: nothing synchronised, nothing allocated (capturable; cam and desc are captured by value)."""
+    check(lib().mrt_camera_path_probes_device(C.byref(cam), C.byref(desc), int(first), int(n), C.c_void_p(d_out_ptr or None), C.c_void_p(stream_ptr)),
+          "mrt_camera_path_probes_device")
+
+
+def pano_probe_range(params, desc, first, n):
+    """mrt_pano_probes (include/mrt.h): the same range for the equirectangular camera of pano_probes."""
+    first, n = _range_args("pano_probe_range", first, n)
+    out = np.zeros(n, dtype=PROBE_DTYPE)
+    check(lib().mrt_pano_probes(C.byref(params), C.byref(desc), first, n, C.c_void_p(out.ctypes.data)), "mrt_pano_probes")
+    return out
+
+
+def pano_probes_device(params, desc, first, n, d_out_ptr, stream_ptr=0):
+    """The same into device records, enqueued on a HIP stream (as camera_path_probes_device)."""
+    check(lib().mrt_pano_probes_device(C.byref(params), C.byref(desc), int(first), int(n), C.c_void_p(d_out_ptr or None), C.c_void_p(stream_ptr)),
+          "mrt_pano_probes_device")
+
+
+def surface_probes(hits, rays=None, sqrt_per_hit=1, seed=0, first_id=0):
+    """mrt_surface_probes (include/mrt.h): sqrt_per_hit^2 cosine-distributed probes leaving the point of
+    each HIT_DTYPE record (Renderer.cast_rays' output), stratified on a jittered grid, from the streams
+    keyed by first_id + j under `seed` -- a PROBE_DTYPE array, hit-major.  rays (the RAY_DTYPE records
+    that were cast, optional) turn each normal towards its ray and give the probes its time.  A miss
+    (mat == NO_HIT) gives a null record: mask by mat.  pi * mean(L) over a hit's probes estimates the
+    irradiance there."""
+    h = np.asarray(hits)
+    if h.dtype != HIT_DTYPE:
+        raise ValueError("surface_probes: hits must be a HIT_DTYPE array")
+    h = np.ascontiguousarray(h).reshape(-1)
+    r = None
+    if rays is not None:
+        r = _as_rays(rays)
+        if r.size != h.size:
+            raise ValueError("surface_probes: rays and hits differ in length")
+    sq = int(sqrt_per_hit)
+    if sq < 0 or sq >= 2 ** 32:
+        raise ValueError("surface_probes: sqrt_per_hit outside uint32")
+    total = h.size * sq * sq
+    out = np.zeros(total if total < 2 ** 32 else 0, dtype=PROBE_DTYPE)
+    check(lib().mrt_surface_probes(C.c_void_p(h.ctypes.data), C.c_void_p(r.ctypes.data if r is not None else None), h.size, sq,
+                                   int(seed) & _U64, int(first_id) & _U64, C.c_void_p(out.ctypes.data)), "mrt_surface_probes")
+    return out
+
+
+def surface_probes_device(d_hits_ptr, d_rays_ptr, n_hits, d_out_ptr, sqrt_per_hit=1, seed=0, first_id=0, stream_ptr=0):
+    """The same on device records (torch data_ptr()s of n_hits mrt_hit, n_hits mrt_ray or 0, and
+    n_hits * sqrt_per_hit^2 mrt_probe, 16-byte aligned), enqueued on a HIP stream: nothing synchronised,
+    nothing allocated (capturable: a replay reads whatever the hit records then hold)."""
+    check(lib().mrt_surface_probes_device(C.c_void_p(d_hits_ptr or None), C.c_void_p(d_rays_ptr or None), int(n_hits), int(sqrt_per_hit),
+                                          int(seed) & _U64, int(first_id) & _U64, C.c_void_p(d_out_ptr or None), C.c_void_p(stream_ptr)),
+          "mrt_surface_probes_device")
+
+
 def _as_radiance(rad, group):
     a = np.asarray(rad)
     if a.dtype != RADIANCE_DTYPE:
@@ -129,6 +219,13 @@ def radiance_fold_device(d_rad_ptr, n_groups, group, d_rgb_ptr, max_luminance=10
     16-byte aligned), enqueued on a HIP stream."""
     check(lib().mrt_radiance_fold_device(C.c_void_p(d_rad_ptr or None), n_groups, group, max_luminance, C.c_void_p(d_rgb_ptr or None),
                                          C.c_void_p(stream_ptr)), "mrt_radiance_fold_device")
+
+
+def radiance_rays_device(d_rad_ptr, n, d_rays_ptr, stream_ptr=0):
+    """mrt_radiance_rays_device (include/mrt.h): adds the ray counts of n device RADIANCE records to the
+    device uint64 at d_rays_ptr (zeroed by the caller), enqueued on a HIP stream."""
+    check(lib().mrt_radiance_rays_device(C.c_void_p(d_rad_ptr or None), int(n), C.c_void_p(d_rays_ptr or None), C.c_void_p(stream_ptr)),
+          "mrt_radiance_rays_device")
 
 
 def default_params():

@@ -245,6 +245,20 @@ def lib():
     L.mrt_camera_path_probe.restype = st
     L.mrt_pano_probe.argtypes = [C.POINTER(MrtCameraParams), C.POINTER(MrtRenderDesc), C.c_uint32, C.c_uint32, C.c_void_p]
     L.mrt_pano_probe.restype = st
+    u64, u32, vp = C.c_uint64, C.c_uint32, C.c_void_p
+    L.mrt_camera_path_probes.argtypes = [C.POINTER(MrtCamera), C.POINTER(MrtRenderDesc), u64, u32, vp]
+    L.mrt_camera_path_probes_device.argtypes = [C.POINTER(MrtCamera), C.POINTER(MrtRenderDesc), u64, u32, vp, vp]
+    L.mrt_pano_probes.argtypes = [C.POINTER(MrtCameraParams), C.POINTER(MrtRenderDesc), u64, u32, vp]
+    L.mrt_pano_probes_device.argtypes = [C.POINTER(MrtCameraParams), C.POINTER(MrtRenderDesc), u64, u32, vp, vp]
+    L.mrt_camera_pixel_rays.argtypes = [C.POINTER(MrtCamera), u32, u32, u64, u32, vp]
+    L.mrt_camera_pixel_rays_device.argtypes = [C.POINTER(MrtCamera), u32, u32, u64, u32, vp, vp]
+    L.mrt_surface_probes.argtypes = [vp, vp, u32, u32, u64, u64, vp]
+    L.mrt_surface_probes_device.argtypes = [vp, vp, u32, u32, u64, u64, vp, vp]
+    L.mrt_radiance_rays_device.argtypes = [vp, u32, vp, vp]
+    L.mrt_radiance_rays_device.restype = st
+    for f in ("mrt_camera_path_probes", "mrt_pano_probes", "mrt_camera_pixel_rays", "mrt_surface_probes"):
+        getattr(L, f).restype = st
+        getattr(L, f + "_device").restype = st
     _lib = L
     return L
 
@@ -272,4 +286,7 @@ EXPORTS = [
     "mrt_cast_rays", "mrt_cast_rays_device", "mrt_camera_pixel_ray",
     "mrt_probe_seed", "mrt_trace_rays", "mrt_trace_rays_workspace", "mrt_trace_rays_device", "mrt_radiance_fold",
     "mrt_radiance_fold_device", "mrt_camera_path_probe", "mrt_pano_probe",
+    "mrt_camera_path_probes", "mrt_camera_path_probes_device", "mrt_pano_probes", "mrt_pano_probes_device",
+    "mrt_camera_pixel_rays", "mrt_camera_pixel_rays_device", "mrt_surface_probes", "mrt_surface_probes_device",
+    "mrt_radiance_rays_device",
 ]

@@ -37,8 +37,9 @@
 // "focusat X Y: focus=..." (%.9g: -focus with that number renders the same image); a miss prints
 // "focusat X Y: miss" and leaves the focus alone.  With -frames it applies once, to frame 0's camera.
 // -pano renders a 360 x 180 degree equirectangular frame from the camera's position through the
-// radiance queries (mrt_pano_probe -> mrt_trace_rays -> mrt_radiance_fold; exact numerics, either
-// backend), written and tone-mapped as usual: the camera flags give position, look-at (the image
+// radiance queries (mrt_pano_probes -> mrt_trace_rays -> mrt_radiance_fold, on a GPU scene their device
+// forms on one stream with nothing but the pixels copied back; exact numerics, either backend), written
+// and tone-mapped as usual: the camera flags give position, look-at (the image
 // centre) and up; -aperture is ignored (no lens); -gpus above 1 is refused.
 #include <algorithm>
 #include <chrono>
@@ -50,6 +51,8 @@
 #include <thread>
 #include <utility>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../../include/mrt.h"
 
@@ -191,10 +194,11 @@ static int run_sequence(const mrt_params& p, std::vector<mrt_scene*>& scenes, st
 }
 
 // -pano: the frame through the radiance queries instead of mrt_render -- every pixel's samples as
-// equirectangular probes at the camera's position (mrt_pano_probe, the render's grid and keying),
-// traced (mrt_trace_rays, exact contract, either backend) and folded per pixel (mrt_radiance_fold),
-// in pieces of whole pixels of at most about 2^16 records.
-static mrt_status render_pano(mrt_scene* scene, const mrt_camera_params& cp, const mrt_render_desc& d, std::vector<float>& img, uint64_t* rays) {
+// equirectangular probes at the camera's position (the render's grid and keying), traced (exact
+// contract, either backend) and folded per pixel, in pieces of whole pixels.
+// CPU backend: mrt_pano_probes -> mrt_trace_rays -> mrt_radiance_fold on host records, pieces of at
+// most about 2^16 records.
+static mrt_status render_pano_host(mrt_scene* scene, const mrt_camera_params& cp, const mrt_render_desc& d, std::vector<float>& img, uint64_t* rays) {
     const uint64_t ns = (uint64_t)d.sqrt_samples * d.sqrt_samples, npx = (uint64_t)d.width * d.height;
     if (ns > 0xFFFFFFFFull || npx > 0xFFFFFFFFull) return MRT_ERR_INVALID;
     const uint64_t piece_px = std::max<uint64_t>(1, (1u << 16) / ns);
@@ -203,15 +207,51 @@ static mrt_status render_pano(mrt_scene* scene, const mrt_camera_params& cp, con
     *rays = 0;
     for (uint64_t p0 = 0; p0 < npx; p0 += piece_px) {
         const uint32_t m = (uint32_t)std::min(piece_px, npx - p0);
-        for (uint32_t k = 0; k < m; k++)
-            for (uint32_t s = 0; s < ns; s++)
-                if (mrt_status st = mrt_pano_probe(&cp, &d, (uint32_t)(p0 + k), s, &probes[(size_t)k * ns + s])) return st;
+        if (mrt_status st = mrt_pano_probes(&cp, &d, p0 * ns, (uint32_t)(m * ns), probes.data())) return st;
         uint64_t r = 0;
         if (mrt_status st = mrt_trace_rays(scene, probes.data(), (uint32_t)(m * ns), d.max_bounces, rad.data(), &r)) return st;
         *rays += r;
         if (mrt_status st = mrt_radiance_fold(rad.data(), m, (uint32_t)ns, d.max_luminance, img.data() + (size_t)p0 * 4)) return st;
     }
     return MRT_OK;
+}
+
+// GPU scene: the same records never leave the device.  Per piece of whole pixels (at most about
+// MRT_TRACE_PIECE records) mrt_pano_probes_device -> mrt_trace_rays_device -> mrt_radiance_rays_device
+// -> mrt_radiance_fold_device are enqueued on one stream, into buffers and a level workspace allocated
+// once; the frame's pixels and the ray total are copied back once at the end.
+static mrt_status render_pano_device(mrt_scene* scene, int device, const mrt_camera_params& cp, const mrt_render_desc& d, std::vector<float>& img,
+                                     uint64_t* rays) {
+    const uint64_t ns = (uint64_t)d.sqrt_samples * d.sqrt_samples, npx = (uint64_t)d.width * d.height;
+    if (ns > 0xFFFFFFFFull || npx > 0xFFFFFFFFull) return MRT_ERR_INVALID;
+    const uint64_t piece_px = std::min(npx, std::max<uint64_t>(1, MRT_TRACE_PIECE / ns));
+    uint64_t work_bytes = 0, work_min = 0;
+    if (mrt_status st = mrt_trace_rays_workspace(scene, d.max_bounces, &work_bytes, &work_min)) return st;
+    void *d_probes = nullptr, *d_rad = nullptr, *d_img = nullptr, *d_work = nullptr, *d_rays = nullptr;
+    hipStream_t q = nullptr;
+    auto run = [&]() -> mrt_status {
+        if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&q) != hipSuccess) return MRT_ERR_HIP;
+        if (hipMalloc(&d_probes, piece_px * ns * sizeof(mrt_probe)) != hipSuccess || hipMalloc(&d_rad, piece_px * ns * sizeof(mrt_radiance)) != hipSuccess ||
+            hipMalloc(&d_img, npx * 16) != hipSuccess || hipMalloc(&d_work, work_bytes) != hipSuccess || hipMalloc(&d_rays, 8) != hipSuccess)
+            return MRT_ERR_OOM;
+        if (hipMemsetAsync(d_rays, 0, 8, q) != hipSuccess) return MRT_ERR_HIP;
+        for (uint64_t p0 = 0; p0 < npx; p0 += piece_px) {
+            const uint32_t m = (uint32_t)std::min(piece_px, npx - p0), n = (uint32_t)(m * ns);
+            if (mrt_status st = mrt_pano_probes_device(&cp, &d, p0 * ns, n, (mrt_probe*)d_probes, q)) return st;
+            if (mrt_status st = mrt_trace_rays_device(scene, (const mrt_probe*)d_probes, n, d.max_bounces, (mrt_radiance*)d_rad, d_work, work_bytes, q)) return st;
+            if (mrt_status st = mrt_radiance_rays_device((const mrt_radiance*)d_rad, n, (uint64_t*)d_rays, q)) return st;
+            if (mrt_status st = mrt_radiance_fold_device((const mrt_radiance*)d_rad, m, (uint32_t)ns, d.max_luminance, (float*)d_img + (size_t)p0 * 4, q)) return st;
+        }
+        if (hipMemcpyAsync(img.data(), d_img, npx * 16, hipMemcpyDeviceToHost, q) != hipSuccess ||
+            hipMemcpyAsync(rays, d_rays, 8, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
+            return MRT_ERR_HIP;
+        return MRT_OK;
+    };
+    const mrt_status st = run();
+    for (void* b : {d_probes, d_rad, d_img, d_work, d_rays})
+        if (b) (void)hipFree(b);
+    if (q) (void)hipStreamDestroy(q);
+    return st;
 }
 
 int main(int argc, char** argv) {
@@ -446,7 +486,7 @@ int main(int argc, char** argv) {
 
     auto t0 = std::chrono::steady_clock::now();  // main.cpp:375
     std::vector<std::thread> th;
-    if (pano) sts[0] = render_pano(scenes[0], cp, descs[0], img, &rays[0]);
+    if (pano) sts[0] = cpu ? render_pano_host(scenes[0], cp, descs[0], img, &rays[0]) : render_pano_device(scenes[0], 0, cp, descs[0], img, &rays[0]);
     for (int r = 0; r < world && !pano; r++)
         th.emplace_back([&, r] {
             sts[r] = have_adaptive ? mrt_render_adaptive(scenes[r], &descs[r], &ap, img.data(), mom.data(), &rays[r], nullptr)

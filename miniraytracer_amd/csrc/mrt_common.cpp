@@ -14,6 +14,8 @@
 #include <vector>
 
 #include "mrt_internal.h"
+#define MRT_PROBEGEN_PIXEL_RAY_ONLY 1  // the part that needs nothing of the hot path
+#include "mrt_probegen.h"
 #include "../../include/mrt_tonemap.h"
 
 static thread_local std::string g_last_error;
@@ -38,19 +40,14 @@ extern "C" const char* mrt_last_error(void) { return g_last_error.c_str(); }
 extern "C" uint32_t mrt_abi_version(void) { return MRT_ABI_VERSION; }
 
 // The pinhole ray through a pixel centre (include/mrt.h "ray queries"), in the arithmetic of
-// include/mrt_temporal.h step 2: float32, this operation order (this file is built without
+// include/mrt_temporal.h step 2: float32, the operation order of mrt_probegen.h's mrt_gen_pixel_ray,
+// the one definition the range form and the device kernel run too (this file is built without
 // contraction).
 extern "C" mrt_status mrt_camera_pixel_ray(const mrt_camera* cam, uint32_t width, uint32_t height, uint32_t x, uint32_t y, mrt_ray* out) {
     if (!cam || !out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_camera_pixel_ray: null");
     if (width == 0 || height == 0 || x >= width || y >= height) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_camera_pixel_ray: pixel outside the image");
-    const float s = ((float)x + 0.5f) / (float)width, t = ((float)y + 0.5f) / (float)height;
-    memset(out, 0, sizeof *out);
-    for (int k = 0; k < 3; k++) {
-        out->o[k] = cam->origin[k];
-        out->d[k] = ((cam->llcorner[k] + s * cam->horz[k]) + t * cam->vert[k]) - cam->origin[k];
-    }
-    out->time = cam->time0;
-    out->tmax = std::numeric_limits<float>::infinity();
+    const mrt_gen_rec r = mrt_gen_pixel_ray(*cam, width, height, x, y);
+    memcpy(out, &r, sizeof r);
     return MRT_OK;
 }
 

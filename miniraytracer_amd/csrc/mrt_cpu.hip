@@ -44,6 +44,7 @@
 #include "mrt_aux.h"
 #include "mrt_cast.h"
 #include "mrt_probe.h"
+#include "mrt_probegen.h"
 #include "mrt_moments.h"
 #include "../../include/mrt_adaptive.h"
 
@@ -574,43 +575,21 @@ extern "C" void mrt_probe_seed(uint64_t seed, uint64_t path_id, mrt_probe* p) {
     p->rng_inc = rng.inc;
 }
 
-// (pixel, sample) of a desc -> the path's stream and its image coordinates, as render_tiles forms them:
-// the sample grid of main.cpp:319-332 in float, u and v by IEEE division
-static mrt_status probe_path_key(const char* who, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, Pcg& rng, float* u, float* v) {
+// The per-record probe starts: the argument rules here, the arithmetic in mrt_probegen.h -- the one
+// definition the range forms and the device kernels (mrt_probegen.hip) run as well.
+static mrt_status probe_key_check(const char* who, const mrt_render_desc* d, uint32_t pixel, uint32_t sample) {
     if (d->width == 0 || d->height == 0 || d->sqrt_samples == 0) return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": a zero size").c_str());
     const uint64_t sq = d->sqrt_samples, ns = sq * sq;
     if ((uint64_t)pixel >= (uint64_t)d->width * d->height || sample >= ns)
         return mrt_internal_fail(MRT_ERR_INVALID, (std::string(who) + ": pixel or sample outside the render").c_str());
-    const uint32_t x = pixel % d->width, y = pixel / d->width;
-    const uint32_t i = (uint32_t)(sample / sq), j = (uint32_t)(sample % sq);
-    const float dx = ((float)i + 0.5f) / (float)d->sqrt_samples, dy = ((float)j + 0.5f) / (float)d->sqrt_samples;
-    *u = ((float)x + dx) / (float)d->width;
-    *v = ((float)y + dy) / (float)d->height;
-    const uint64_t path_id = (uint64_t)pixel * ns + sample;
-    pcg_seed(rng, splitmix64(d->seed ^ path_id), path_id);
     return MRT_OK;
-}
-
-static void probe_put(mrt_probe* out, f3 o, f3 dir, float time, const Pcg& rng) {
-    memset(out, 0, sizeof *out);
-    out->o[0] = o.x, out->o[1] = o.y, out->o[2] = o.z;
-    out->d[0] = dir.x, out->d[1] = dir.y, out->d[2] = dir.z;
-    out->time = time;
-    out->rng_state = rng.state;
-    out->rng_inc = rng.inc;
 }
 
 extern "C" mrt_status mrt_camera_path_probe(const mrt_camera* cam, const mrt_render_desc* d, uint32_t pixel, uint32_t sample, mrt_probe* out) {
     if (!cam || !d || !out) return mrt_internal_fail(MRT_ERR_INVALID, "mrt_camera_path_probe: null");
-    Pcg rng;
-    float u, v;
-    if (mrt_status st = probe_path_key("mrt_camera_path_probe", d, pixel, sample, rng, &u, &v)) return st;
-    DScene S{};  // camera_ray_args reads the camera through S.camp, nothing else
-    S.camp = cam;
-    f3 o, dir;
-    float time;
-    camera_ray_args(S, rng, u, v, &o, &dir, &time);
-    probe_put(out, o, dir, time, rng);
+    if (mrt_status st = probe_key_check("mrt_camera_path_probe", d, pixel, sample)) return st;
+    const mrt_gen_rec r = gen_camera_probe(cam, gen_grid(d->width, d->height, d->sqrt_samples, d->seed), pixel, sample);
+    memcpy(out, &r, sizeof r);
     return MRT_OK;
 }
 
@@ -624,15 +603,9 @@ extern "C" mrt_status mrt_pano_probe(const mrt_camera_params* p, const mrt_rende
     q.focus_dist = 1.0f;
     mrt_camera cam;
     if (mrt_status st = mrt_make_camera(&q, &cam)) return st;
-    Pcg rng;
-    float s, t;
-    if (mrt_status st = probe_path_key("mrt_pano_probe", d, pixel, sample, rng, &s, &t)) return st;
-    const float phi = (s - 0.5f) * 6.2831855f, theta = (t - 0.5f) * 3.1415927f;
-    const float ct = mrt_cosf(theta);
-    const float a = ct * mrt_sinf(phi), b = mrt_sinf(theta), c = ct * mrt_cosf(phi);
-    const f3 dir = sub(add(fmul(a, ld3(cam.u)), fmul(b, ld3(cam.v))), fmul(c, ld3(cam.w)));
-    const float time = ref_fma(p->time1 - p->time0, randf(rng), p->time0);  // camera.h:41
-    probe_put(out, ld3(cam.origin), dir, time, rng);
+    if (mrt_status st = probe_key_check("mrt_pano_probe", d, pixel, sample)) return st;
+    const mrt_gen_rec r = gen_pano_probe(cam, gen_grid(d->width, d->height, d->sqrt_samples, d->seed), pixel, sample);
+    memcpy(out, &r, sizeof r);
     return MRT_OK;
 }
 
