@@ -18,7 +18,8 @@ OBJDIR   = build/obj
 
 LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
            $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_cast.o $(OBJDIR)/mrt_probe.o $(OBJDIR)/mrt_probegen.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
-           $(OBJDIR)/mrt_temporal.o $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o
+           $(OBJDIR)/mrt_temporal.o $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o \
+           $(OBJDIR)/mrt_mathfn_api.o
 # the path kernels twice: exact contract (no contraction, IEEE division) and tolerance contract
 # (FMA contraction, reciprocal division, hardware rcp/sqrt/rsq, f32 transcendentals)
 # (-fno-hip-fp32-correctly-rounded-divide-sqrt: f32 division by v_rcp_f32 + multiply instead of
@@ -107,6 +108,13 @@ $(OBJDIR)/mrt_adaptive.o: $(CSRC)/mrt_adaptive.hip include/mrt_adaptive.h $(HDRS
 $(OBJDIR)/mrt_temporal.o: $(CSRC)/mrt_temporal.hip include/mrt_temporal.h include/mrt_denoise.h $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# the contract's transcendentals as array calls (mrt_mathfn[_d][_device]), host and device from
+# include/mrt_mathfn.h under the exact contract's flags (the host's explicit fma() as one instruction,
+# as in the CPU backend): a translation unit of its own
+$(OBJDIR)/mrt_mathfn_api.o: $(CSRC)/mrt_mathfn_api.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(HIPDEV) $(if $(HOSTFMA),-Xarch_host $(HOSTFMA)) -c $< -o $@
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)

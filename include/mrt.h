@@ -581,6 +581,31 @@ mrt_status mrt_surface_probes(const mrt_hit* hits, const mrt_ray* rays /* may be
 mrt_status mrt_surface_probes_device(const mrt_hit* d_hits, const mrt_ray* d_rays /* may be NULL */, uint32_t n_hits, uint32_t sqrt_per_hit,
                                      uint64_t seed, uint64_t first_id, mrt_probe* d_out, void* stream);
 
+/* ---- the contract's transcendentals as array calls --------------------------------------------
+ * The functions of include/mrt_mathfn.h that the formulas above are written in (and the tone map's
+ * and the filter's), on arrays: out[i] = f(a[i]) or f(a[i], b[i]), each one evaluation in double and
+ * one rounding to float, the same bits on the host and on the device.  The trigonometric functions
+ * are defined for |x| < 2^20 (and +-inf and NaN, which give NaN); a finite argument past that is
+ * outside the contract.  `b` is read by MRT_FN_ATAN2 and MRT_FN_POW only and may be NULL otherwise.
+ * mrt_mathfn_device is enqueued on `stream` (a hipStream_t), allocates and synchronises nothing, can
+ * be captured, runs one thread per element and writes exactly n results.  MRT_ERR_INVALID for a null
+ * pointer or an unknown `which`; n == 0 is a no-op. */
+enum {
+    MRT_FN_SIN = 0, MRT_FN_COS = 1, MRT_FN_TAN = 2, MRT_FN_LOG = 3, MRT_FN_LOG10 = 4, MRT_FN_ASIN = 5, MRT_FN_EXP = 6,
+    MRT_FN_POW5 = 7,  /* x^5 */
+    MRT_FN_ATAN2 = 8, /* atan2(a, b) */
+    MRT_FN_POW = 9    /* pow(a, b): a^5 by MRT_FN_POW5's products when b == 5 */
+};
+mrt_status mrt_mathfn(uint32_t which, uint32_t n, const float* a, const float* b, float* out);
+mrt_status mrt_mathfn_device(uint32_t which, uint32_t n, const float* d_a, const float* d_b, float* d_out, void* stream);
+/* The double cores those functions round, called exactly as the header defines them, on double
+ * arrays: mrt_sincos_d (out = sin, out2 = cos; |a| < 2^20), mrt_log_d, mrt_exp_d, mrt_atan2_d(a, b).
+ * `out2` is written by MRT_FND_SINCOS only and may be NULL otherwise, `b` is read by MRT_FND_ATAN2
+ * only.  The same contract as above: host and device give the same bits. */
+enum { MRT_FND_SINCOS = 0, MRT_FND_LOG = 1, MRT_FND_EXP = 2, MRT_FND_ATAN2 = 3 };
+mrt_status mrt_mathfn_d(uint32_t which, uint32_t n, const double* a, const double* b, double* out, double* out2);
+mrt_status mrt_mathfn_d_device(uint32_t which, uint32_t n, const double* d_a, const double* d_b, double* d_out, double* d_out2, void* stream);
+
 /* ---- multi-GPU: the framebuffer gather over RCCL (xGMI) ---------------------------------------
  * The reference's seam is main.cpp:347-382 (the worker threads over one work_queue) writing
  * G_linearBackBuffer (main.cpp:58): here each rank renders the work_queue tiles dealt to it

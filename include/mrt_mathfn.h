@@ -39,7 +39,10 @@ __device__ static inline double mrt_dc_dev(double c) {
 #define MRT_DC(x) (x)
 #endif
 
-/* ---- sin / cos: Cody-Waite reduction by pi/2 (|x| < 2^20), Taylor kernels on [-pi/4, pi/4] ---- */
+/* ---- sin / cos: Cody-Waite reduction by pi/2 (|x| < 2^20), Taylor kernels on [-pi/4, pi/4] ----
+ * The contract ends at |x| < 2^20: past it the two-term reduction loses accuracy, and from |k| >= 2^63
+ * the (long long)k conversion is undefined in C, so host and device may differ on finite arguments out
+ * there.  +-inf and NaN give NaN on both sides (r is NaN whatever the quadrant). */
 MRT_HD void mrt_sincos_d(double x, double* s, double* c) {
     const double two_over_pi = 6.36619772367581382433e-01;
     const double pio2_1 = 1.57079632673412561417e+00;  /* first 33 bits of pi/2 */

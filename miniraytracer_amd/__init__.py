@@ -586,6 +586,64 @@ def tonemap_device(d_rgb_ptr, n, d_lwmax_ptr, d_argb_ptr, stream_ptr=0, reduce=T
           "mrt_tonemap_device")
 
 
+MATHFN = ("sin", "cos", "tan", "log", "log10", "asin", "exp", "pow5", "atan2", "pow")  # include/mrt.h MRT_FN_*
+MATHFN_D = ("sincos", "log", "exp", "atan2")  # include/mrt.h MRT_FND_*
+
+
+def _fn_index(names, name):
+    if name not in names:
+        raise ValueError(f"mathfn: unknown function {name!r} (one of {', '.join(names)})")
+    return names.index(name)
+
+
+def mathfn(name, a, b=None):
+    """The numerics contract's float function `name` of MATHFN (include/mrt_mathfn.h) over float32
+    arrays on the host: f(a), atan2(a, b), pow(a, b)."""
+    w = _fn_index(MATHFN, name)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if w >= 8:
+        if b is None:
+            raise ValueError(f"mathfn: {name} takes two arrays")
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        if b.shape != a.shape:
+            raise ValueError("mathfn: a and b must have one shape")
+    out = np.zeros(a.shape, dtype=np.float32)
+    check(lib().mrt_mathfn(w, a.size, a.ctypes.data, b.ctypes.data if w >= 8 else None, out.ctypes.data), "mrt_mathfn")
+    return out
+
+
+def mathfn_device(name, n, a_ptr, b_ptr, out_ptr, stream=0):
+    """The same on the device (torch data_ptr()s of n floats each; b_ptr may be 0 for the one-argument
+    functions), enqueued on a HIP stream: one thread per element, exactly n results."""
+    check(lib().mrt_mathfn_device(_fn_index(MATHFN, name), n, C.c_void_p(a_ptr or None), C.c_void_p(b_ptr or None), C.c_void_p(out_ptr or None),
+                                  C.c_void_p(stream)), "mrt_mathfn_device")
+
+
+def mathfn_d(name, a, b=None):
+    """The double core `name` of MATHFN_D (mrt_sincos_d, mrt_log_d, mrt_exp_d, mrt_atan2_d(a, b)) over
+    float64 arrays on the host; "sincos" returns (sin, cos)."""
+    w = _fn_index(MATHFN_D, name)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if w == 3:
+        if b is None:
+            raise ValueError("mathfn_d: atan2 takes two arrays")
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != a.shape:
+            raise ValueError("mathfn_d: a and b must have one shape")
+    out = np.zeros(a.shape, dtype=np.float64)
+    out2 = np.zeros(a.shape, dtype=np.float64) if w == 0 else None
+    check(lib().mrt_mathfn_d(w, a.size, a.ctypes.data, b.ctypes.data if w == 3 else None, out.ctypes.data,
+                             out2.ctypes.data if w == 0 else None), "mrt_mathfn_d")
+    return (out, out2) if w == 0 else out
+
+
+def mathfn_d_device(name, n, a_ptr, b_ptr, out_ptr, out2_ptr=0, stream=0):
+    """The same on the device (torch data_ptr()s of n doubles each; out2_ptr receives "sincos"'s cosines
+    and may be 0 otherwise, b_ptr may be 0 but for "atan2"), enqueued on a HIP stream."""
+    check(lib().mrt_mathfn_d_device(_fn_index(MATHFN_D, name), n, C.c_void_p(a_ptr or None), C.c_void_p(b_ptr or None), C.c_void_p(out_ptr or None),
+                                    C.c_void_p(out2_ptr or None), C.c_void_p(stream)), "mrt_mathfn_d_device")
+
+
 def default_denoise_params():
     """mrt_denoise_params with the library's defaults (iterations, sigma_color, sigma_normal,
     sigma_albedo, sigma_depth)."""

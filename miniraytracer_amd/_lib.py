@@ -259,6 +259,12 @@ def lib():
     for f in ("mrt_camera_path_probes", "mrt_pano_probes", "mrt_camera_pixel_rays", "mrt_surface_probes"):
         getattr(L, f).restype = st
         getattr(L, f + "_device").restype = st
+    L.mrt_mathfn.argtypes = [u32, u32, vp, vp, vp]
+    L.mrt_mathfn_device.argtypes = [u32, u32, vp, vp, vp, vp]
+    L.mrt_mathfn_d.argtypes = [u32, u32, vp, vp, vp, vp]
+    L.mrt_mathfn_d_device.argtypes = [u32, u32, vp, vp, vp, vp, vp]
+    for f in ("mrt_mathfn", "mrt_mathfn_device", "mrt_mathfn_d", "mrt_mathfn_d_device"):
+        getattr(L, f).restype = st
     _lib = L
     return L
 
@@ -288,5 +294,5 @@ EXPORTS = [
     "mrt_radiance_fold_device", "mrt_camera_path_probe", "mrt_pano_probe",
     "mrt_camera_path_probes", "mrt_camera_path_probes_device", "mrt_pano_probes", "mrt_pano_probes_device",
     "mrt_camera_pixel_rays", "mrt_camera_pixel_rays_device", "mrt_surface_probes", "mrt_surface_probes_device",
-    "mrt_radiance_rays_device",
+    "mrt_radiance_rays_device", "mrt_mathfn", "mrt_mathfn_device", "mrt_mathfn_d", "mrt_mathfn_d_device",
 ]

@@ -51,6 +51,8 @@ def lib():
                                  C.c_void_p]
         L.oracle_mathfn.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oracle_mathfn.restype = None
+        L.oracle_mathfn_d.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_mathfn_d.restype = None
         _lib = L
     return _lib
 
@@ -125,6 +127,20 @@ def mathfn(name, a, b=None):
     out = np.zeros(a.shape, dtype=np.float32)
     lib().oracle_mathfn(MATHFN.index(name), a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data)
     return out
+
+
+MATHFN_D = ("sincos", "log", "exp", "atan2")
+
+
+def mathfn_d(name, a, b=None):
+    """include/mrt_mathfn.h's double core `name` of MATHFN_D over float64 arrays (atan2(a, b)); "sincos"
+    returns (sin, cos)."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(a if b is None else b, dtype=np.float64)
+    assert a.shape == b.shape
+    out, out2 = np.zeros(a.shape, dtype=np.float64), np.zeros(a.shape, dtype=np.float64)
+    lib().oracle_mathfn_d(MATHFN_D.index(name), a.size, a.ctypes.data, b.ctypes.data, out.ctypes.data, out2.ctypes.data)
+    return (out, out2) if name == "sincos" else out
 
 
 def pdf(scene, node, rows, states, seq):

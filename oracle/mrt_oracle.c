@@ -942,3 +942,16 @@ void oracle_mathfn(uint32_t which, uint32_t n, const float* a, const float* b, f
         }
     }
 }
+
+/* The double cores those functions round, as array calls (tests/test_mathfn_gpu.py).  which: 0 mrt_sincos_d
+ * (out = sin, out2 = cos), 1 mrt_log_d, 2 mrt_exp_d (b, out2 unused), 3 mrt_atan2_d(a[i], b[i]). */
+void oracle_mathfn_d(uint32_t which, uint32_t n, const double* a, const double* b, double* out, double* out2) {
+    for (uint32_t i = 0; i < n; i++) {
+        switch (which) {
+        case 0: mrt_sincos_d(a[i], &out[i], &out2[i]); break;
+        case 1: out[i] = mrt_log_d(a[i]); break;
+        case 2: out[i] = mrt_exp_d(a[i]); break;
+        default: out[i] = mrt_atan2_d(a[i], b[i]); break;
+        }
+    }
+}

@@ -60,6 +60,8 @@ void oracle_samplers(uint64_t initstate, uint64_t initseq, uint32_t n, uint32_t 
 /* include/mrt_mathfn.h as array calls: which 0 sin, 1 cos, 2 tan, 3 log, 4 log10, 5 asin, 6 exp, 7 pow5
  * (of a[i]), 8 atan2(a[i], b[i]), 9 pow(a[i], b[i]) */
 void oracle_mathfn(uint32_t which, uint32_t n, const float* a, const float* b, float* out);
+/* its double cores: which 0 mrt_sincos_d (out sin, out2 cos), 1 mrt_log_d, 2 mrt_exp_d, 3 mrt_atan2_d(a[i], b[i]) */
+void oracle_mathfn_d(uint32_t which, uint32_t n, const double* a, const double* b, double* out, double* out2);
 
 #ifdef __cplusplus
 }

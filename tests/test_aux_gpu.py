@@ -4,7 +4,8 @@ mrt_denoise, both enqueued on a stream and capturable."""
 import numpy as np
 import pytest
 
-from test_aux_host import bits, black_cornell, cornell_16spp, params, random_guides, ref_scene, rmse, seq_mean
+from test_aux_host import (EDGE_SIGMA_NORMALS, bits, black_cornell, cornell_16spp, edge_weight_frames, params, random_guides, ref_scene, rmse,
+                           seq_mean)
 
 pytestmark = pytest.mark.gpu
 
@@ -149,6 +150,15 @@ def test_device_filter_equals_host_filter(gpu, w, h, it):
     nrm[..., :3] += np.float32(2.0) * (nrm[..., :3] != 0)
     img = rng.random((h, w, 4)).astype(np.float32)
     p = params(gpu, it, sigma_color=1.0, sigma_normal=4.0, sigma_albedo=0.8, sigma_depth=1.5)
+    assert np.array_equal(bits(device_denoise(gpu, img, nrm, alb, p)), bits(gpu.denoise(img, nrm, alb, p)))
+
+
+@pytest.mark.parametrize("sn", EDGE_SIGMA_NORMALS)
+def test_device_filter_equals_host_filter_at_the_edges_of_exp_and_pow(gpu, sn):
+    """tests/test_aux_host.py edge_weight_frames: summed exponents 0 ... ~110, so float-subnormal and
+    exactly-zero weights, under sigma_normal 0.25, 5 (mrt_powf's pow5 shortcut) and 128."""
+    img, nrm, alb, (it, kw) = edge_weight_frames(sn)
+    p = params(gpu, it, **kw)
     assert np.array_equal(bits(device_denoise(gpu, img, nrm, alb, p)), bits(gpu.denoise(img, nrm, alb, p)))
 
 

@@ -318,6 +318,55 @@ def test_filter_equals_its_formulas_in_float64(mrt, w, h, it):
     assert np.abs(out[..., :3] - img[..., :3]).max() > 1e-3 or w == 1  # it did filter
 
 
+EDGE_SIGMA_NORMALS = [0.25, 5.0, 128.0]  # 5: mrt_powf's pow5 shortcut; 128: the library default's order
+
+
+def edge_weight_frames(sigma_normal, w=37, h=23):
+    """(img, nrm, alb, params) whose weights sit at the edges of mrt_expf / mrt_powf: colours and albedos are
+    constant per 6 x 6 block plus 1 % noise, so the summed exponent e_z + e_a + e_c of a tap is ~0 inside a
+    block and up to ~110 across blocks (sigma_color 0.19, sigma_albedo 0.155, colours in [0, 1)): weights that
+    are ordinary, float-subnormal (exponent 87.3 ... 104) and exactly zero (past 104) in one frame, twice --
+    the second pass quarters sigma_color^2."""
+    rng = np.random.default_rng(7)  # one frame for every sigma_normal
+    nrm, alb = random_guides(rng, h, w)
+    nrm[..., :3] += np.float32(2.0) * (nrm[..., :3] != 0)
+    by, bx = np.arange(h)[:, None] // 6, np.arange(w)[None, :] // 6
+    blocks = lambda: rng.random((h // 6 + 1, w // 6 + 1, 3))[by, bx]
+    img = np.zeros((h, w, 4), dtype=np.float32)
+    img[..., :3] = (0.99 * blocks() + 0.01 * rng.random((h, w, 3))).astype(np.float32)
+    img[..., 3] = rng.random((h, w)).astype(np.float32)
+    alb[..., :3] = (0.99 * blocks() + 0.01 * rng.random((h, w, 3))).astype(np.float32)
+    return img, nrm, alb, (2, dict(sigma_color=0.19, sigma_normal=sigma_normal, sigma_albedo=0.155, sigma_depth=1.5))
+
+
+def first_pass_exponents(img, alb, sc, sa, sz):
+    """e_z + e_a + e_c of the right-hand and the upper neighbour taps of pass 0, in float64."""
+    out = []
+    for a, b in ((np.s_[:, :-1], np.s_[:, 1:]), (np.s_[:-1], np.s_[1:])):
+        c, q = img.astype(np.float64), alb.astype(np.float64)
+        zp, zq = q[a][..., 3], q[b][..., 3]
+        ez = np.where(zp != zq, np.abs(zp - zq) / np.where(zp != zq, np.maximum(zp, zq) * sz, 1), 0)
+        out.append((ez + ((q[a][..., :3] - q[b][..., :3]) ** 2).sum(-1) / sa ** 2 + ((c[a][..., :3] - c[b][..., :3]) ** 2).sum(-1) / sc ** 2).ravel())
+    return np.concatenate(out)
+
+
+@pytest.mark.parametrize("sn", EDGE_SIGMA_NORMALS)
+def test_filter_with_weights_at_the_edges_of_exp_and_pow(mrt, sn):
+    """The float64 restatement's bound on frames with float-subnormal and exactly-zero weights.  No pixel is
+    left out: the centre tap's weight is exactly 9/64, so sum w is never below it, let alone subnormal, and
+    the bound's reasoning (relative error of the weights that matter, colours in [0, 1)) holds everywhere."""
+    img, nrm, alb, (it, kw) = edge_weight_frames(sn)
+    e = first_pass_exponents(img, alb, kw["sigma_color"], kw["sigma_albedo"], kw["sigma_depth"])
+    assert e.min() < 0.5 and ((e > 87.4) & (e < 103.9)).any() and (e > 104.0).any() and 100 < e.max() < 125, (e.min(), e.max())
+    p = params(mrt, it, **kw)
+    out = mrt.denoise(img, nrm, alb, p)
+    want = filter_f64(img, nrm, alb, p)
+    err = np.abs(out[..., :3] - want[..., :3]).max()
+    print(f"sigma_normal {sn}: exponents {e.min():.3f} .. {e.max():.1f}, max |host - float64| {err:.3e}")
+    assert err < BOUND
+    assert np.abs(out[..., :3] - img[..., :3]).max() > 1e-3  # it did filter
+
+
 # ---------------------------------------------------------------- 5. purpose
 def cornell_16spp(mrt, device, numerics="exact"):
     g = np.load(os.path.join(GOLDEN, "shipped_stream_5_small.npz"))

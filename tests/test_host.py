@@ -270,6 +270,48 @@ def test_tonemap_formula_with_libm(mrt):
             assert all(abs(a - b) <= 1 for a, b in zip(got, c))
 
 
+def tonemap_edge_frames():
+    """The pixels the comments of include/mrt_tonemap.h argue about, as (name, frame [n, 4], checks): each
+    check is (pixel, mask, value) with argb[pixel] & mask == value, worked out by hand from the header:
+
+    * a NaN channel makes lum, lum_new and all three products NaN; vmin(NaN, 1) keeps 1: 255, 255, 255.
+      NaN never wins the maximum (L_wmax < NaN is false), so the other pixels map as without it;
+    * a negative channel beside a positive luminance: lum_new > 0, the product is negative, the channel 0;
+    * a negative luminance: mrt_powf of a negative base is NaN, and all three channels are 255;
+    * an infinite channel: L_wmax = inf, so invlogmax = 1 / log10(inf) = 0, scale = 0, invmax = 0.  A finite
+      pixel of positive channels has pow(lum * 0, bias) = 0, lum_new = 0 * (log(lum + 1) / log 2) = 0 and packs
+      to 0; the infinite pixel has inf * 0 = NaN into mrt_powf and packs to 255, 255, 255;
+    * an all-black frame: L_wmax = 0, invmax = 1 / 0 = inf, and 0 * inf = NaN into mrt_powf: 0x00FFFFFF in
+      every pixel, for +0 and for -0 channels."""
+    f = np.float32
+    base = np.array([[0.2, 0.4, 0.1, 0.0], [1.5, 0.3, 2.5, 0.0], [0.01, 0.02, 0.03, 0.0]], dtype=f)
+    nan, inf, W = f(np.nan), f(np.inf), 0xFFFFFF
+    frames = []
+    frames.append(("nan", np.concatenate([base, np.array([[nan, 0.5, 0.5, 0], [0.5, nan, 0.5, 0], [0.5, 0.5, nan, 0]], dtype=f)]),
+                   [(3, W, W), (4, W, W), (5, W, W)]))
+    frames.append(("negative", np.concatenate([base, np.array([[-0.5, 1, 1, 0], [1, 1, -0.25, 0], [-1, -1, -1, 0], [-0.5, 0.1, 0.1, 0]], dtype=f)]),
+                   [(3, 0xFF0000, 0), (4, 0x0000FF, 0), (5, W, W), (6, W, W)]))
+    frames.append(("infinite", np.concatenate([base, np.array([[inf, 1, 1, 0], [1, inf, inf, 0]], dtype=f)]),
+                   [(0, W, 0), (1, W, 0), (2, W, 0), (3, W, W), (4, W, W)]))
+    black = np.zeros((70, 4), dtype=f)
+    black[1::2, :3] = f(-0.0)
+    frames.append(("black", black, [(i, W, W) for i in range(70)]))
+    return frames
+
+
+@pytest.mark.parametrize("case", tonemap_edge_frames(), ids=lambda c: c[0])
+def test_tonemap_edge_pixels(mrt, case):
+    """NaN, negative and infinite channels and the all-black frame on the host form: the hand-derived bytes,
+    and no other pixel changes because a NaN pixel is in the frame."""
+    name, frame, checks = case
+    argb = mrt.tonemap_argb(frame.reshape(1, -1, 4)).reshape(-1)
+    assert (argb >> 24 == 0).all()
+    for px, mask, value in checks:
+        assert int(argb[px]) & mask == value, (name, px, hex(int(argb[px])))
+    if name == "nan":
+        assert np.array_equal(argb[:3], mrt.tonemap_argb(frame[:3].reshape(1, -1, 4)).reshape(-1))
+
+
 def test_select_scene_errors_are_loud(mrt, tmp_path):
     with pytest.raises(mrt.MrtError):
         mrt.select_scene(8, 1.0, asset_dir=str(tmp_path))  # no bunny asset -> MRT_ERR_IO

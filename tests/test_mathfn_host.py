@@ -17,9 +17,11 @@ adjacent floats, the true value rounds where r rounds, and the result must equal
 argument -- r within 2^-41 of a float or a midpoint, or a result that differs from float32(r) -- is
 evaluated by mpmath.
 
-No device hook: on the device the same header is compiled (mrt_device.h sin_, log_, ...), and the
-device side of these functions stays covered by the render parities, which compare the kernels with this
-host code bit for bit."""
+The device side: the same header compiled for gfx950 is not the host's code (its double division, square
+root, rint and conversions are instruction sequences of their own), and the render parities reach it only
+at the arguments the scenes produce.  tests/test_mathfn_gpu.py evaluates the ten functions and their double
+cores on the device through mrt_mathfn_device / mrt_mathfn_d_device, on the argument sets generated here
+(trig_args, log_args, ... special_values) and on further edges, and requires the bits of this host code."""
 import mpmath as mp
 import numpy as np
 import pytest
@@ -128,44 +130,69 @@ def test_logarithms(orc, name):
     assert_share(name, [check(orc, name, x), check(orc, name, around_one)])
 
 
-def test_asin(orc):
-    rng = np.random.default_rng(13)
+def asin_args(seed):
+    rng = np.random.default_rng(seed)
     x = rng.uniform(-1.0, 1.0, N).astype(F32)
     top = [F32(1.0)]
     for _ in range(1 << 12):
         top.append(np.nextafter(top[-1], F32(0)))
     top = np.array(top[1:], dtype=F32)
     small = np.ldexp(rng.uniform(0.5, 1.0, 4096), rng.integers(-100, 0, 4096)).astype(F32)
-    assert_share("asin", [check(orc, "asin", x), check(orc, "asin", np.concatenate([top, -top, small, -small]))])
+    return x, np.concatenate([top, -top, small, -small])
+
+
+def test_asin(orc):
+    x, edges = asin_args(13)
+    assert_share("asin", [check(orc, "asin", x), check(orc, "asin", edges)])
+
+
+def exp_args(seed):
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-104.0, 89.0, N).astype(F32)
+    small = np.ldexp(rng.uniform(0.5, 1.0, 4096), rng.integers(-60, 0, 4096)).astype(F32)
+    return x, np.concatenate([small, -small])
 
 
 def test_exp(orc):
-    rng = np.random.default_rng(14)
-    x = rng.uniform(-104.0, 89.0, N).astype(F32)
-    small = np.ldexp(rng.uniform(0.5, 1.0, 4096), rng.integers(-60, 0, 4096)).astype(F32)
-    assert_share("exp", [check(orc, "exp", x), check(orc, "exp", np.concatenate([small, -small]))])
+    x, small = exp_args(14)
+    assert_share("exp", [check(orc, "exp", x), check(orc, "exp", small)])
+
+
+def pow5_args(seed):
+    rng = np.random.default_rng(seed)
+    x = np.concatenate([rng.uniform(0.0, 1.0, N // 2), np.ldexp(rng.uniform(0.5, 1.0, N // 2), rng.integers(-30, 26, N // 2))]).astype(F32)
+    return x, -x[:4096]
 
 
 def test_pow5(orc):
-    rng = np.random.default_rng(15)
-    x = np.concatenate([rng.uniform(0.0, 1.0, N // 2), np.ldexp(rng.uniform(0.5, 1.0, N // 2), rng.integers(-30, 26, N // 2))]).astype(F32)
-    assert_share("pow5", [check(orc, "pow5", x), check(orc, "pow5", -x[:4096])])
+    x, neg = pow5_args(15)
+    assert_share("pow5", [check(orc, "pow5", x), check(orc, "pow5", neg)])
 
 
-def test_atan2(orc):
-    rng = np.random.default_rng(16)
+def atan2_args(seed):
+    """((y, x) across the exponents, (y, x) of random directions)."""
+    rng = np.random.default_rng(seed)
     y = (np.ldexp(rng.uniform(0.5, 1.0, N), rng.integers(-40, 41, N)) * rng.choice([-1.0, 1.0], N)).astype(F32)
     x = (np.ldexp(rng.uniform(0.5, 1.0, N), rng.integers(-40, 41, N)) * rng.choice([-1.0, 1.0], N)).astype(F32)
     unit = rng.normal(size=(2, N // 4)).astype(F32)  # directions: sphere_uv's arguments
-    assert_share("atan2", [check(orc, "atan2", y, x), check(orc, "atan2", unit[0], unit[1])])
+    return (y, x), (unit[0], unit[1])
 
 
-def test_pow_on_the_tone_map_s_domain(orc):
-    rng = np.random.default_rng(17)
+def test_atan2(orc):
+    wide, unit = atan2_args(16)
+    assert_share("atan2", [check(orc, "atan2", *wide), check(orc, "atan2", *unit)])
+
+
+def pow_args(seed):
+    rng = np.random.default_rng(seed)
     x = rng.uniform(0.0, 1.0, N).astype(F32)
     y = rng.uniform(0.0, 2.0, N).astype(F32)
     keep = (x > 0) & (y > 0)
-    assert_share("pow", [check(orc, "pow", x[keep], y[keep])])
+    return x[keep], y[keep]
+
+
+def test_pow_on_the_tone_map_s_domain(orc):
+    assert_share("pow", [check(orc, "pow", *pow_args(17))])
 
 
 def same(a, b):
@@ -174,35 +201,42 @@ def same(a, b):
     return bool((((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b)))).all())
 
 
-def test_special_values(orc):
+def special_values():
+    """The special values as rows (function, arguments, wanted float; NaN = any NaN): IEEE's, and the
+    atan2 quadrant / signed-zero / infinity table of C99 F.9.1.4."""
     z, nz = F32(0.0), F32(-0.0)
     pi = np.float64(np.pi)
-    one = lambda name, *a: orc.mathfn(name, *[[v] for v in a])[0]
+    rows = []
     for name in ("sin", "tan", "asin"):
-        assert same(one(name, z), z) and same(one(name, nz), nz), name
+        rows += [(name, (z,), z), (name, (nz,), nz)]
     for name in ("sin", "cos", "tan"):
-        assert np.isnan(one(name, NAN)), name
-    assert same(one("cos", z), 1.0) and same(one("cos", nz), 1.0)
-    assert same(one("asin", F32(1)), F32(pi / 2)) and same(one("asin", F32(-1)), F32(-pi / 2))
-    assert np.isnan(one("asin", F32(1.5))) and np.isnan(one("asin", NAN)) and np.isnan(one("asin", np.nextafter(F32(1), INF)))
+        rows += [(name, (NAN,), NAN)]
+    rows += [("cos", (z,), F32(1)), ("cos", (nz,), F32(1))]
+    rows += [("asin", (F32(1),), F32(pi / 2)), ("asin", (F32(-1),), F32(-pi / 2))]
+    rows += [("asin", (F32(1.5),), NAN), ("asin", (NAN,), NAN), ("asin", (np.nextafter(F32(1), INF),), NAN)]
     for name in ("log", "log10"):
-        assert same(one(name, z), -INF) and same(one(name, nz), -INF) and same(one(name, F32(1)), z), name
-        assert np.isnan(one(name, F32(-1))) and np.isnan(one(name, NAN)) and same(one(name, INF), INF), name
-    assert same(one("log10", F32(1000)), 3.0) and same(one("log10", F32(0.5) ** 0 * F32(1e10)), 10.0)
-    assert same(one("exp", z), 1.0) and same(one("exp", nz), 1.0) and same(one("exp", -INF), z) and same(one("exp", INF), INF)
-    assert np.isnan(one("exp", NAN)) and same(one("exp", F32(89)), INF) and same(one("exp", F32(-104)), z)
-    assert same(one("pow5", z), z) and same(one("pow5", nz), nz) and same(one("pow5", INF), INF) and same(one("pow5", F32(2)), 32.0)
-    assert np.isnan(one("pow5", NAN)) and same(one("pow5", F32(-2)), -32.0)
-    # atan2(y, x): the quadrant / signed-zero / infinity table of C99 F.9.1.4
+        rows += [(name, (z,), -INF), (name, (nz,), -INF), (name, (F32(1),), z)]
+        rows += [(name, (F32(-1),), NAN), (name, (NAN,), NAN), (name, (INF,), INF)]
+    rows += [("log10", (F32(1000),), F32(3)), ("log10", (F32(0.5) ** 0 * F32(1e10),), F32(10))]
+    rows += [("exp", (z,), F32(1)), ("exp", (nz,), F32(1)), ("exp", (-INF,), z), ("exp", (INF,), INF)]
+    rows += [("exp", (NAN,), NAN), ("exp", (F32(89),), INF), ("exp", (F32(-104),), z)]
+    rows += [("pow5", (z,), z), ("pow5", (nz,), nz), ("pow5", (INF,), INF), ("pow5", (F32(2),), F32(32))]
+    rows += [("pow5", (NAN,), NAN), ("pow5", (F32(-2),), F32(-32))]
     table = [(z, F32(1), z), (nz, F32(1), nz), (z, F32(-1), F32(pi)), (nz, F32(-1), F32(-pi)), (z, z, z), (nz, z, nz),
              (z, nz, F32(pi)), (nz, nz, F32(-pi)), (F32(1), z, F32(pi / 2)), (F32(-1), z, F32(-pi / 2)), (F32(1), nz, F32(pi / 2)),
              (F32(-1), nz, F32(-pi / 2)), (F32(1), INF, z), (F32(-1), INF, nz), (F32(1), -INF, F32(pi)), (F32(-1), -INF, F32(-pi)),
              (INF, F32(1), F32(pi / 2)), (-INF, F32(1), F32(-pi / 2)), (INF, INF, F32(pi / 4)), (-INF, INF, F32(-pi / 4)),
              (INF, -INF, F32(3 * pi / 4)), (-INF, -INF, F32(-3 * pi / 4)), (F32(1), F32(1), F32(pi / 4)), (F32(-1), F32(-1), F32(-3 * pi / 4))]
-    for y, x, want in table:
-        assert same(one("atan2", y, x), want), (float(y), float(x), float(one("atan2", y, x)), float(want))
-    assert np.isnan(one("atan2", NAN, F32(1))) and np.isnan(one("atan2", F32(1), NAN))
+    rows += [("atan2", (y, x), want) for y, x, want in table]
+    rows += [("atan2", (NAN, F32(1)), NAN), ("atan2", (F32(1), NAN), NAN)]
     # pow on the tone map's domain: x in [0, 1], y > 0
-    assert same(one("pow", F32(0.3), z), 1.0) and same(one("pow", F32(1), F32(1.7)), 1.0) and same(one("pow", z, F32(0.5)), z)
-    assert same(one("pow", F32(0.25), F32(0.5)), 0.5) and same(one("pow", F32(0.5), F32(2)), 0.25) and same(one("pow", F32(0.5), F32(5)), F32(0.03125))
-    assert np.isnan(one("pow", NAN, F32(0.5))) and np.isnan(one("pow", F32(-0.5), F32(0.5)))
+    rows += [("pow", (F32(0.3), z), F32(1)), ("pow", (F32(1), F32(1.7)), F32(1)), ("pow", (z, F32(0.5)), z)]
+    rows += [("pow", (F32(0.25), F32(0.5)), F32(0.5)), ("pow", (F32(0.5), F32(2)), F32(0.25)), ("pow", (F32(0.5), F32(5)), F32(0.03125))]
+    rows += [("pow", (NAN, F32(0.5)), NAN), ("pow", (F32(-0.5), F32(0.5)), NAN)]
+    return rows
+
+
+def test_special_values(orc):
+    for name, args, want in special_values():
+        got = orc.mathfn(name, *[[v] for v in args])[0]
+        assert same(got, want), (name, [float(v) for v in args], float(got), float(want))
