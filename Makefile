@@ -16,7 +16,7 @@ HIPDEV   = -mllvm -disable-promote-alloca-to-vector -mllvm -structurizecfg-skip-
 CSRC     = miniraytracer_amd/csrc
 OBJDIR   = build/obj
 
-LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
+LIB_OBJS = $(OBJDIR)/mrt_render.o $(OBJDIR)/mrt_fold.o $(OBJDIR)/mrt_upload.o $(OBJDIR)/mrt_query.o $(OBJDIR)/mrt_kernels_exact.o $(OBJDIR)/mrt_kernels_fast.o $(OBJDIR)/mrt_kernels_fastz.o \
            $(OBJDIR)/mrt_kernels_pex.o $(OBJDIR)/mrt_aux.o $(OBJDIR)/mrt_cast.o $(OBJDIR)/mrt_probe.o $(OBJDIR)/mrt_probegen.o $(OBJDIR)/mrt_denoise.o $(OBJDIR)/mrt_adaptive.o \
            $(OBJDIR)/mrt_temporal.o $(OBJDIR)/mrt_cpu.o $(OBJDIR)/mrt_tables.o $(OBJDIR)/scene_builder.o $(OBJDIR)/mrt_common.o $(OBJDIR)/mrt_comm.o \
            $(OBJDIR)/mrt_mathfn_api.o

@@ -1,7 +1,7 @@
 // mrt_aux.h -- first-hit feature buffers (include/mrt.h "feature buffers and denoise"): what one
 // camera ray contributes, written once for the device kernel (mrt_aux.hip, mrt_aux_kernel<F>) and
 // the CPU backend (mrt_cpu.hip), and the interface between mrt_aux.hip and the launch in
-// mrt_render.hip.  The kernels live in a translation unit of their own, built under the exact
+// mrt_query.hip.  The kernels live in a translation unit of their own, built under the exact
 // numerics contract, with a table of their own: the path-kernel objects (mrt_kernels.hip, the
 // KernelTable of mrt_launch.h) do not change with them.
 #pragma once

@@ -1,7 +1,7 @@
 // mrt_cast.h -- batched ray queries (include/mrt.h "ray queries"): what one caller ray yields,
 // written once for the device kernel (mrt_cast.hip, mrt_cast_kernel<F>) and the CPU backend
 // (mrt_cpu.hip, mrt_cpu_cast_rays), and the interface between mrt_cast.hip and the launch in
-// mrt_render.hip.  Like the feature buffers (mrt_aux.h) the kernels live in a translation unit of
+// mrt_query.hip.  Like the feature buffers (mrt_aux.h) the kernels live in a translation unit of
 // their own, built under the exact numerics contract, with a table of their own: the path-kernel
 // objects (mrt_kernels.hip, the KernelTable of mrt_launch.h) do not change with them.
 #pragma once

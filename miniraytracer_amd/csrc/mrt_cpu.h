@@ -1,4 +1,4 @@
-// mrt_cpu.h -- the CPU backend (mrt_cpu.hip) as seen from the C-ABI entry points (mrt_render.hip):
+// mrt_cpu.h -- the CPU backend (mrt_cpu.hip) as seen from the C-ABI entry points (mrt_render.hip, mrt_upload.hip, mrt_query.hip):
 // a scene uploaded to MRT_DEVICE_CPU carries one of these instead of device tables.
 #pragma once
 #include "../../include/mrt.h"

@@ -5,6 +5,12 @@
 #include "../../include/mrt.h"
 
 mrt_status mrt_internal_fail(mrt_status s, const char* msg);
+// a failed HIP call ends the calling entry point with MRT_ERR_HIP and the call's text (HIP units only)
+#define HIPCHK(x)                                                                                   \
+    do {                                                                                            \
+        hipError_t e_ = (x);                                                                        \
+        if (e_ != hipSuccess) return mrt_internal_fail(MRT_ERR_HIP, (std::string(#x) + ": " + hipGetErrorString(e_)).c_str()); \
+    } while (0)
 std::string mrt_internal_package_dir();
 
 // work_queue tile list in the reference order: row-major tiles re-ordered along the inverted

@@ -975,7 +975,7 @@ __global__ void __launch_bounds__(TreeOf<F>::wg) __attribute__((amdgpu_waves_per
 // to finish clears the list for the next launch.  (The launch's ray count stays the fast paths'.)
 // The Cornell variant at eight waves per SIMD, that is at most 64 VGPRs (one spilled): under
 // MRT_RF_FOLD_ASYNC its waves run beside the next launch's path kernel, each in the slot a 64-VGPR
-// path wave left free (mrt_render.hip kSideSlots).  The other variants' launches keep their grids
+// path wave left free (mrt_context.h kSideSlots).  The other variants' launches keep their grids
 // and their retrace its registers.
 template <uint32_t F>
 static constexpr bool kRetrace = MRT_TABLE_PEX && MRT_FWD_FOLD && (F & FT_BIASED) != 0 && !kPathExact<F>;

@@ -1,4 +1,4 @@
-// mrt_launch.h -- the interface between the host code (mrt_render.hip) and the path-kernel
+// mrt_launch.h -- the interface between the host code (mrt_render.hip, mrt_upload.hip) and the path-kernel
 // translation unit (mrt_kernels.hip), which is compiled twice: once under the exact numerics
 // contract (MRT_FAST=0, -ffp-contract=off) and once under the tolerance contract (MRT_FAST=1,
 // FMA contraction, hardware reciprocal/sqrt, f32 transcendentals).  DESIGN.md "Numerics contracts".

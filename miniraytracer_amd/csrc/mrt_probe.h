@@ -1,7 +1,7 @@
 // mrt_probe.h -- radiance queries (include/mrt.h "radiance queries"): what one caller record yields,
 // written once for the device kernel (mrt_probe.hip, mrt_probe_kernel<F>) and the CPU backend
 // (mrt_cpu.hip, mrt_cpu_trace_rays), and the interface between mrt_probe.hip and the launches in
-// mrt_render.hip.  Like the ray queries (mrt_cast.h) the kernels live in a translation unit of their
+// mrt_query.hip.  Like the ray queries (mrt_cast.h) the kernels live in a translation unit of their
 // own, built under the exact numerics contract, with a table of their own: the path-kernel objects
 // (mrt_kernels.hip, the KernelTable of mrt_launch.h) do not change with them.
 #pragma once

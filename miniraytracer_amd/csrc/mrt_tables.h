@@ -1,6 +1,6 @@
 // mrt_tables.h -- the device-side scene tables, built on the host from a mrt_scene_view by the
 // scene compiler (mrt_tables.hip, host code only) and used by both backends: the GPU uploads them
-// to HBM (mrt_render.hip mrt_scene_upload), the CPU backend keeps them in host memory (mrt_cpu.hip)
+// to HBM (mrt_upload.hip mrt_scene_upload), the CPU backend keeps them in host memory (mrt_cpu.hip)
 // and walks them with the same hot-path code.
 #pragma once
 #include <vector>

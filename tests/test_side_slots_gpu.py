@@ -1,4 +1,4 @@
-"""MRT_RF_FOLD_ASYNC with side slots (mrt_render.hip kSideSlots): the Cornell walk kernel, whose one-wave
+"""MRT_RF_FOLD_ASYNC with side slots (mrt_context.h kSideSlots): the Cornell walk kernel, whose one-wave
 groups fill every SIMD, is launched with fewer groups, and the launch's retrace and fold run in the freed wave
 slots on the context's own stream while the caller's stream goes on to the next launch.  Per-path
 streams make the result independent of which wave runs a path: every async render here equals the
@@ -10,7 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 MRT_NPART = 8  # mrt_launch.h
-SIDE = 768     # mrt_render.hip kSideSlots
+SIDE = 768     # mrt_context.h kSideSlots
 
 
 @pytest.fixture(scope="module")

@@ -16,7 +16,7 @@ GPU leg            the kernel picked is the entry's literal; the exact contract 
                    under the hooks whose walk runs that build.
 
 The feature / kernel literals are worked out by hand from scene_features (mrt_tables.hip) and
-pick_variant (mrt_render.hip, mrt_launch.h kVariants): index 0-2 the shape-specialised walks, 3-7 the narrower
+pick_variant (mrt_upload.hip, mrt_launch.h kVariants): index 0-2 the shape-specialised walks, 3-7 the narrower
 interpreters, 8 the catch-all interpreter 0x3FFF, 9 the generic machine 0x37FF.
 """
 import ctypes as C

@@ -9,7 +9,7 @@ set -e
 cd "$(dirname "$0")/.."
 tag=$1; shift
 flags="$*"
-make -s build/obj/scene_builder.o build/obj/mrt_common.o build/obj/mrt_render.o build/obj/mrt_kernels_exact.o build/obj/mrt_cpu.o build/obj/mrt_tables.o build/obj/mrt_comm.o \
+make -s build/obj/scene_builder.o build/obj/mrt_common.o build/obj/mrt_render.o build/obj/mrt_fold.o build/obj/mrt_upload.o build/obj/mrt_query.o build/obj/mrt_kernels_exact.o build/obj/mrt_cpu.o build/obj/mrt_tables.o build/obj/mrt_comm.o \
     build/obj/mrt_aux.o build/obj/mrt_denoise.o build/obj/mrt_adaptive.o build/obj/mrt_temporal.o
 mkdir -p exp/obj_$tag
 BASE="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-fast-math -fno-slp-vectorize -w -mllvm -disable-promote-alloca-to-vector -mllvm -structurizecfg-skip-uniform-regions -DMRT_EXPERIMENTS"
@@ -33,11 +33,16 @@ if [ -n "${EXACT_FLAGS// /}" ]; then
   /opt/rocm/bin/hipcc $BASE -ffp-contract=off -DMRT_FAST=0 $EXACT_FLAGS -c miniraytracer_amd/csrc/mrt_kernels.hip -o exp/obj_$tag/mrt_kernels_exact.o
   EX=exp/obj_$tag/mrt_kernels_exact.o
 fi
-RO=build/obj/mrt_render.o
-if [ -n "${HOST_FLAGS:-}" ]; then  # host TU too (e.g. -DMRT_PATH_WG=..., which both sides must agree on)
-  /opt/rocm/bin/hipcc $BASE -ffp-contract=off $HOST_FLAGS -c miniraytracer_amd/csrc/mrt_render.hip -o exp/obj_$tag/mrt_render.o
-  RO=exp/obj_$tag/mrt_render.o
-fi
+HOST_UNITS="mrt_render mrt_fold mrt_upload mrt_query"  # the units that launch kernels
+RO=""
+for u in $HOST_UNITS; do
+  if [ -n "${HOST_FLAGS:-}" ]; then  # host TUs too (e.g. -DMRT_PATH_WG=..., which both sides must agree on)
+    /opt/rocm/bin/hipcc $BASE -ffp-contract=off $HOST_FLAGS -c miniraytracer_amd/csrc/$u.hip -o exp/obj_$tag/$u.o
+    RO="$RO exp/obj_$tag/$u.o"
+  else
+    RO="$RO build/obj/$u.o"
+  fi
+done
 PX=build/obj/mrt_kernels_pex.o  # the path-exact variants as in the Makefile (run MRT_PATH_EXACT=0 to A/B them)
 make -s $PX
 if [ -n "${PEX_FLAGS:-}" ]; then  # ... or built with extra flags

@@ -2,8 +2,8 @@
 // pool_tail32, pool_index32, pool_take32) against the 64-bit expressions of the path kernel's claim()
 // that it replaces, stand-alone on the CPU for a sanitizer build (`make claim-check`: AddressSanitizer
 // + UBSan, host code only, nothing preloaded; no GPU code runs).  Launches of 1 path up to the largest
-// the host accepts (0xFFFFFFFF / npix whole samples, and 2^32 - 1 paths), partitioned as mrt_render.hip
-// partitions them; counter answers at a partition's start, at the launch's last path, around every
+// the host accepts (0xFFFFFFFF / npix whole samples, and 2^32 - 1 paths), partitioned by the render's own
+// plan_partitions (mrt_plan.h) for each group shape the library builds; counter answers at a partition's start, at the launch's last path, around every
 // edge (the partition's end, one claim before it, the tail zone's edge), past the partition's end and
 // past 2^32; pools that hold 0, 1 and 63 paths when 1, 33 or 64 lanes take one, so that a claim
 // straddles the pool and a partition's end.  Every result must agree exactly.
@@ -11,7 +11,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "../miniraytracer_amd/csrc/mrt_launch.h"
+#include "../miniraytracer_amd/csrc/mrt_plan.h"
 
 using namespace mrtd;
 
@@ -74,12 +74,17 @@ int main() {
     const uint32_t launches[] = {1u, 63u, 64u, 129u, 500u, 8191u, 8193u, 8460u, 2099601u, 6759999u,
                                  0xFFFFFFFFu / npix * npix,  // the most whole samples of a 500 x 500 image
                                  0xFFFFFFFFu};
-    const uint64_t grid = 8192;  // one-wave groups of a 256-CU launch
+    // the three group shapes the library builds, each with its grid on 256 CUs: one-wave groups at eight
+    // waves per SIMD, 4-wave groups at seven, the 12-wave treelet groups at six
+    const struct { uint32_t waves; uint64_t grid; } shapes[] = {{1, 8192}, {4, 1792}, {12, 512}};
+    for (const auto& shape : shapes)
     for (uint32_t n_paths : launches) {
-        // mrt_render.hip's partitions and tail zone
-        const uint32_t tail_zone = (uint32_t)umin64(grid * 2 * MRT_BATCH, n_paths);
-        uint64_t part_base[MRT_NPART + 1];
-        for (uint32_t k = 0; k <= MRT_NPART; k++) part_base[k] = (uint64_t)n_paths * k / MRT_NPART;
+        const uint64_t grid = shape.grid;
+        // the partitions and tail zone of the launch as the render plans them (mrt_plan.h)
+        PathParams P{};
+        plan_partitions(P, n_paths, (int)grid, shape.waves);
+        const uint32_t tail_zone = P.tail_zone;
+        const uint64_t* const part_base = P.part_base;
         for (uint32_t k = 0; k < MRT_NPART; k++) {
             const uint64_t p0 = part_base[k], pe = part_base[k + 1];
             const uint64_t tz = tail_zone / MRT_NPART;
